@@ -14,6 +14,13 @@ fraction of the HBM roofline.
   rate (4 B/element) is reported beside it.
 * N > 1: one process per GPU (torchrun), each rank reduces its own shard
   (weak scaling, no data-path collective: the elements are independent).
+* A plain run sets up, warms up, times the K steps, writes --dump-outputs when
+  asked and prints the JSON line (`value`, `ms_per_step`, and the roofline
+  fraction from the HIP events around those same K steps).  Every item below
+  that takes runs of its own -- the parity check before timing, roofline
+  `traffic` and the cold-cache launch, cpu_baseline, host_path, the
+  per-(op, type) / pack / RMA / HBM-probe tables and the N > 1 children --
+  runs only under --full.
 * roofline: algorithmic bytes per launch / mean kernel duration from HIP
   events on the launch stream, against 8 TB/s (MI355X_MICROARCH.md).
   `traffic` comes from the committed rocprofv3 PMC summary (FETCH_SIZE
@@ -51,6 +58,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything reported beside `value`: the parity check, "
+                         "host path, per-(op, type) / pack / RMA / HBM-probe / cold-cache tables, the CPU "
+                         "baselines and, at N > 1, the collective configs (the --no-* flags prune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left in `inout` to DIR/<name>.npy (float32; a fixed "
+                         "seeded sample when the buffer exceeds the dump limit)")
     ap.add_argument("--sweep", action="store_true",
                     help="time the probe library's combine variants next to the product kernel (rank 0 stderr)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -1014,6 +1028,27 @@ def rma_self_roofline(L, C, torch, dev, n):
             "frac": round(gbs / HBM_PEAK_GBS, 4), "correct": correct}
 
 
+DUMP_MAX_BYTES = 32 << 20      # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out_dir, torch, acc, rank, world):
+    """--dump-outputs: the `inout` buffer as the last timed step left it (what
+    a caller of msx_reduce_local_dev receives), as float32 in
+    DIR/inout.npy (N = 1) or DIR/inout_rank<r>.npy.  A buffer larger than this
+    rank's share of DUMP_MAX_BYTES is sampled at sorted indices drawn from a
+    fixed seed, the same for every run of the same --elems and --gpus."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, keep = acc.numel(), DUMP_MAX_BYTES // 4 // world
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0xD5EED).integers(0, n, keep))
+        got = acc[torch.from_numpy(idx).to(acc.device)].cpu().numpy()
+    else:
+        got = acc.cpu().numpy()
+    name = "inout.npy" if world == 1 else f"inout_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), np.ascontiguousarray(got, dtype=np.float32))
+
+
 def launch_ranks(args):
     """`bench.py --gpus N` without a launcher: start N rank processes of this
     script (one per GPU: LOCAL_RANK = rank; on a box with fewer GPUs they share
@@ -1085,8 +1120,10 @@ def main():
     os.environ["MSX_SIZE"], os.environ["MSX_RANK"], os.environ["MSX_DEVICE"] = "1", "0", str(local)
     L = msx.init(errors_return=True)
     C = msx.C
-    from msx import probe
-    P = probe.lib()                          # bench-only measurement kernels
+    P = None
+    if args.full or args.sweep:
+        from msx import probe
+        P = probe.lib()                      # bench-only measurement kernels
 
     n = args.elems
     g = torch.Generator(device=dev).manual_seed(0x5EED + rank)
@@ -1101,13 +1138,14 @@ def main():
         if rc:
             raise RuntimeError(f"msx_reduce_local_dev: {rc} {msx.last_error()}")
 
-    # correctness of the timed kernel on this exact data (one IEEE add / element)
-    ref = acc + src
-    step()
-    torch.cuda.synchronize()
-    if not torch.equal(acc.view(torch.int32), ref.view(torch.int32)):
-        raise RuntimeError("parity check failed before timing")
-    del ref
+    if args.full:
+        # correctness of the timed kernel on this exact data (one IEEE add / element)
+        ref = acc + src
+        step()
+        torch.cuda.synchronize()
+        if not torch.equal(acc.view(torch.int32), ref.view(torch.int32)):
+            raise RuntimeError("parity check failed before timing")
+        del ref
 
     sweep = {}
     if args.sweep and rank == 0:
@@ -1191,16 +1229,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kern_ms_max = float(t[0]), float(t[1])
 
+    # before anything below reduces into `acc` again
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, acc, rank, world)
+
+    # Everything from here to the JSON line is reported beside `value` and
+    # takes runs of its own: --full only.
+    full = args.full
     # N > 1: the collective configs in child MPI processes (not part of
     # `value`), under one wall budget (run_children)
     kids = None
-    if world > 1 and not args.no_collectives:
+    if full and world > 1 and not args.no_collectives:
         kids = run_children(dist, world, rank, local, args.coll_scale, n, torch.cuda.device_count() >= world,
                             args.no_host_path)
     # host-memory path (the MPI buffers start and end in host memory): measured
     # on rank 0 only, reported beside the device-resident value.
     host = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if full and rank == 0 and world == 1 and not args.no_host_path:
         host = {}
         a_h = src.cpu()
         for label, pin, mode in (("pageable", False, 0), ("pageable_staged", False, 2),
@@ -1249,16 +1294,16 @@ def main():
         host["device_blocking_MPI_Reduce_local_GiB_s"] = round(n * BYTES_PER_ELEM / dt_b / 2**30, 1)
 
     per_op = None
-    if rank == 0 and world == 1 and not args.no_per_op:
+    if full and rank == 0 and world == 1 and not args.no_per_op:
         per_op = per_op_roofline(L, C, torch, dev, stream, n * 4)
     pack = None
-    if rank == 0 and world == 1 and not args.no_pack:
+    if full and rank == 0 and world == 1 and not args.no_pack:
         pack = pack_roofline(L, C, torch, dev, stream)
     rma = hbm = cold = None
-    if rank == 0 and world == 1 and not args.no_per_op:
+    if full and rank == 0 and world == 1 and not args.no_per_op:
         rma = rma_self_roofline(L, C, torch, dev, n)
         hbm = hbm_ceiling_probe(P, torch, dev, stream, n * 4)
-    if rank == 0:
+    if full and rank == 0:
         # SURVEY.md §7 "use cold buffers": the headline launch with the Infinity
         # Cache flushed first, reported in `roofline` beside the back-to-back frac
         cold = cold_cache_launch(P, torch, dev, stream, src, acc, n, mixes=(world == 1 and not args.no_per_op))
@@ -1267,7 +1312,7 @@ def main():
         total_bytes = world * args.steps * n * BYTES_PER_ELEM
         value = total_bytes / elapsed / 2**30
         achieved = n * BYTES_PER_ELEM / (kern_ms / 1e3) / 1e9      # GB/s, rank 0's kernel
-        traffic = traffic_from_profiles()
+        traffic = traffic_from_profiles() if full else None
         out = {
             "metric": "GiB/s device-resident MPI_SUM local-reduce fp32 (HBM traffic, 12 B/element)",
             "value": round(value, 2),
@@ -1321,7 +1366,7 @@ def main():
             out["infinity_cache"] = cold
         if sweep:
             out["variant_sweep_GB_s"] = sweep
-        if world == 1:
+        if full and world == 1:
             del src, acc
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, n)

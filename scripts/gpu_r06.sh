@@ -37,18 +37,18 @@ test)
         -p no:cacheprovider
     ;;
 bench)
-    step bench_n1 600 python bench.py
+    step bench_n1 600 python bench.py --full
     ;;
 rehearse)
     MSX_BENCH_VARIANTS_AT=8 MSX_BENCH_TEST_HANG=ipc:3 MSX_BENCH_WALL_S=300 MSX_BENCH_LOG=$OUT/coll_n8.log \
-        step bench_n8_hang 420 python bench.py --gpus 8 --steps 20 --warmup 5
+        step bench_n8_hang 420 python bench.py --full --gpus 8 --steps 20 --warmup 5
     ;;
 prof)
     # kernel trace + stats of the default N = 1 bench command, then FETCH_SIZE
     # and WRITE_SIZE in separate --pmc passes (the guide's HBM section:
     # FETCH_SIZE x 2 on gfx950) over the device-side tables
-    B="bench.py --no-host-path --no-collectives --cpu-seconds 1"
-    step prof_trace 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python bench.py
+    B="bench.py --full --no-host-path --no-collectives --cpu-seconds 1"
+    step prof_trace 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python bench.py --full
     step pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o pmc_fetch --output-format csv -- python $B
     step pmc_write 240 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o pmc_write --output-format csv -- python $B
     ;;
@@ -64,7 +64,7 @@ treegeom)
 rehearse_clean)
     # the default N = 8 sequence with every rank on this box's one GPU (no hang)
     MSX_BENCH_VARIANTS_AT=8 MSX_BENCH_LOG=$OUT/coll_n8_clean.log \
-        step bench_n8_clean 500 python bench.py --gpus 8 --steps 20 --warmup 5
+        step bench_n8_clean 500 python bench.py --full --gpus 8 --steps 20 --warmup 5
     ;;
 measure)
     run_mode bench && run_mode geom && run_mode prof && run_mode rehearse

@@ -27,6 +27,42 @@ def test_cpu_info_and_median_helpers():
     assert k == 20 and len(calls) == 23 and t >= 0          # 3 warm-ups + 20 timed
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a buffer within the limit is written whole, a larger one
+    as the same seeded sample on every call; float32, one file per rank."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    acc = torch.arange(10000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), torch, acc, 0, 1)
+    whole = np.load(tmp_path / "a" / "inout.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, acc.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), torch, acc, 1, 2)
+    s1, s2 = (np.load(tmp_path / d / "inout_rank1.npy") for d in ("b", "c"))
+    assert s1.dtype == np.float32 and s1.shape == (500,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and np.isin(s1, whole).all() and len(np.unique(s1)) > 400
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    """A plain command line leaves --full and --dump-outputs off; --steps and
+    --warmup are taken as given."""
+    sys.path.insert(0, REPO)
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+        sys.argv += ["--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "d"
+    finally:
+        sys.argv = argv
+
+
 def test_threaded_collective_baseline_is_correct():
     """oracle/msx_oracle_threads.c (bench.py cpu_baseline_collectives): p
     threads as ranks run the reference's Rabenseifner allreduce / recursive-

@@ -221,7 +221,8 @@ int local_combine(const OpRef& op, MPI_Datatype dt, const void* in, void* inout,
 }
 
 // ---------------------------------------------------------------------------
-// collectives: single-rank forms here, multi-rank forms in the transport engine
+// collectives: single-rank forms here, multi-rank forms in the engine
+// (msx_collectives.cpp, engine_*)
 // ---------------------------------------------------------------------------
 // MPIR_Localcopy (mpid/pt2pt.cpp:770-948): a predefined type is one memcpy,
 // a derived one goes through the pack / unpack kernels (non-contiguous copy).

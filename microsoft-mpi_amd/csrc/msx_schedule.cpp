@@ -1,0 +1,229 @@
+// msx_schedule.cpp — the pure schedule functions ("schedules" in
+// msx_transport.h): algorithm gates, Rabenseifner blocks and the rank trees.
+// Host arithmetic only; exported for the host-side tests.
+#include "msx_transport.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include "msx_dtype.h"
+
+namespace msx {
+
+// ===========================================================================
+// schedules
+// ===========================================================================
+int pof2_floor(int p)
+{
+    int v = 1;
+    while (v * 2 <= p) v *= 2;
+    return v;
+}
+
+int newrank_of(int rank, int p)
+{
+    const int rem = p - pof2_floor(p);
+    if (rank < 2 * rem) return (rank & 1) ? rank / 2 : -1;
+    return rank - rem;
+}
+
+int real_of_newrank(int n, int p)
+{
+    const int rem = p - pof2_floor(p);
+    return n < rem ? 2 * n + 1 : n + rem;
+}
+
+Leaf leaf_of(int n, int p)
+{
+    // fold: odd rank 2n+1 computes MPID_Uop_call(tmp=x_{2n}, recvbuf=x_{2n+1})
+    // (reduce.cpp:3858-3865): inout = x_{2n+1}, in = x_{2n}.
+    const int rem = p - pof2_floor(p);
+    Leaf l;
+    if (n < rem) { l.a = 2 * n + 1; l.b = 2 * n; }
+    else { l.a = n + rem; }
+    return l;
+}
+
+// The flat communicators' algorithm switch points (Mpi.SwitchoverSettings
+// [COLL_SWITCHOVER_FLAT], mpid/env.cpp:514-608): MPICH_DEFAULT_*_MSG override
+// the coll.h defaults as env_to_int does (common/mpiutil.cpp:65-91): unset or
+// longer than the 11-character buffer -> default, else _wtoi's value,
+// clamped below at 0.  Read once; every rank must see the same environment,
+// as with the reference.
+namespace {
+uint32_t env_switch(const char* name, int defval)
+{
+    const char* v = getenv(name);
+    if (!v || strlen(v) > 11) return (uint32_t)defval;
+    long long x = strtoll(v, nullptr, 10);           // _wtoi: leading blanks, sign, digits
+    if (x > INT32_MAX) x = INT32_MAX;
+    if (x < 0) x = 0;                                // minval 0
+    return (uint32_t)x;
+}
+struct SwitchPoints {
+    uint32_t allreduce_short = env_switch("MPICH_DEFAULT_ALLREDUCE_SHORT_MSG", 262144);
+    uint32_t reduce_short = env_switch("MPICH_DEFAULT_REDUCE_SHORT_MSG", 65536);
+    uint32_t redscat_long = env_switch("MPICH_DEFAULT_REDSCAT_COMMUTATIVE_LONG_MSG", 524288);
+};
+const SwitchPoints& switch_points()
+{
+    static const SwitchPoints sp;
+    return sp;
+}
+}  // namespace
+
+int allreduce_algo(int p, size_t count, int type_size, bool builtin)
+{
+    // reduce.cpp:3884-3888; count*type_size is evaluated in 32 bits.
+    const uint32_t nbytes = (uint32_t)((uint64_t)count * (uint64_t)type_size);
+    if (nbytes <= switch_points().allreduce_short || !builtin || count < (size_t)pof2_floor(p))
+        return A_RECURSIVE_DOUBLING;
+    return A_RABENSEIFNER;
+}
+
+int reduce_scatter_algo(int p, size_t total_count, int type_size, bool commutative)
+{
+    (void)p;
+    if (!commutative) return -1;
+    // reduce.cpp:1705-1709: nbytes = (unsigned)(total_count * type_size) wraps at 4 GiB.
+    const uint32_t nbytes = (uint32_t)((uint64_t)total_count * (uint64_t)type_size);
+    return nbytes < switch_points().redscat_long ? A_RS_HALVING : A_RS_PAIRWISE;
+}
+
+static int log2i(int v)
+{
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+
+static int bitrev(int x, int bits)
+{
+    int r = 0;
+    for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1) << (bits - 1 - i);
+    return r;
+}
+
+void allreduce_block(int p, size_t count, int j, size_t* start, size_t* len)
+{
+    const int pof2 = pof2_floor(p);
+    const size_t rs = count / (size_t)pof2, es = count % (size_t)pof2;
+    *start = (size_t)j * rs;
+    *len = rs + (j == pof2 - 1 ? es : 0);   // endSize on the last block (:3935-3936)
+}
+
+// Recursive halving with mask = 1, 2, 4, ... keeps the lower half when the
+// newrank bit is 0: the final block of newrank n is bitrev(n).
+int allreduce_block_of_newrank(int p, int n) { return bitrev(n, log2i(pof2_floor(p))); }
+int allreduce_block_owner(int p, int j) { return bitrev(j, log2i(pof2_floor(p))); }
+
+static RankTree tree_from_leaves(int p, const int* leaf_newranks, int P)
+{
+    RankTree t;
+    t.P = P;
+    t.chain = false;
+    t.pairmask = 0;
+    for (int i = 0; i < 32; ++i) t.src[i] = -1;
+    for (int k = 0; k < P; ++k) {
+        Leaf l = leaf_of(leaf_newranks[k], p);
+        t.src[2 * k] = l.a;
+        if (l.b >= 0) {
+            t.src[2 * k + 1] = l.b;
+            t.pairmask |= 1u << k;
+        }
+    }
+    return t;
+}
+
+RankTree tree_allreduce(int p, int n)
+{
+    const int P = pof2_floor(p);
+    int lv[16];
+    for (int k = 0; k < P; ++k) lv[k] = n ^ k;   // step mask pairs with n^mask
+    return tree_from_leaves(p, lv, P);
+}
+
+RankTree tree_reduce_scatter(int p, int n)
+{
+    const int P = pof2_floor(p);
+    const int bits = log2i(P);
+    int lv[16];
+    for (int k = 0; k < P; ++k) lv[k] = n ^ bitrev(k, bits);   // masks P/2, ..., 1
+    return tree_from_leaves(p, lv, P);
+}
+
+int reduce_algo(int p, size_t count, int type_size, bool builtin)
+{
+    // reduce.cpp:151: (unsigned)(count*type_size) > reduce_short_msg (64 KiB by default)
+    const uint32_t nbytes = (uint32_t)((uint64_t)count * (uint64_t)type_size);
+    return (nbytes > switch_points().reduce_short && builtin && count >= (size_t)pof2_floor(p)) ? A_RABENSEIFNER
+                                                                                                : A_BINOMIAL;
+}
+
+int gate_type_size(MPI_Datatype dt, bool nbc)
+{
+    if (dtype_is_derived(dt)) {            // user ops only; the builtin gates never see one
+        const Dtype* t = dtype_lookup(dt);
+        return t ? (int)(nbc ? t->extent : t->size) : 0;
+    }
+    return nbc ? type_size(dt) : (int)dtype_size(dt);
+}
+
+RankTree tree_reduce_rsag(int p, int n)
+{
+    // MPI_Reduce folds the ODD rank into the even one below it (reduce.cpp:
+    // 136-165: Uop(tmp = x_{2n+1}, recvbuf = x_{2n})), newrank n -> real 2n.
+    const int P = pof2_floor(p), rem = p - P;
+    RankTree t;
+    t.P = P;
+    for (int i = 0; i < 32; ++i) t.src[i] = -1;
+    for (int k = 0; k < P; ++k) {
+        const int m = n ^ k;
+        if (m < rem) {
+            t.src[2 * k] = 2 * m;
+            t.src[2 * k + 1] = 2 * m + 1;
+            t.pairmask |= 1u << k;
+        } else {
+            t.src[2 * k] = m + rem;
+        }
+    }
+    return t;
+}
+
+RankTree tree_ireduce_rsag(int p, int n, int root)
+{
+    // IreduceBuildScatterGatherTaskList (reduce.cpp:6267-6670) runs the same
+    // fold and recursive halving over ranks RELATIVE TO THE ROOT: peer =
+    // RankAdd(TrimmedToOriginalRankEven(rem, s ^ offset), root) (:6471), the
+    // even relative rank combining Uop(tmp = x_{rel+1}, recvbuf) (:6403-6411).
+    RankTree t = tree_reduce_rsag(p, n);
+    for (int i = 0; i < 32; ++i)
+        if (t.src[i] >= 0) t.src[i] = (t.src[i] + root) % p;
+    return t;
+}
+
+RankTree tree_reduce_binomial(int p, int root)
+{
+    // relrank k receives from k|mask (reduce.cpp:489-537): a balanced tree over
+    // relative ranks with the leaves >= p absent
+    RankTree t;
+    int P = 1;
+    while (P < p) P *= 2;
+    t.P = P;
+    t.nleaves = p;
+    for (int i = 0; i < 32; ++i) t.src[i] = -1;
+    for (int k = 0; k < p; ++k) t.src[2 * k] = (k + root) % p;
+    return t;
+}
+
+RankTree tree_pairwise(int p, int r)
+{
+    RankTree t;
+    t.P = p;
+    t.chain = true;
+    for (int i = 0; i < 32; ++i) t.src[i] = -1;
+    for (int k = 0; k < p; ++k) t.src[k] = ((r - k) % p + p) % p;   // src = r-1, r-2, ...
+    return t;
+}
+
+}  // namespace msx

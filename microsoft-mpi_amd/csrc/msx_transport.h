@@ -1,5 +1,10 @@
 // msx_transport.h — multi-rank bootstrap, peer mapping and the collective engine.
 //
+// Implemented by msx_transport.cpp (hub, barrier, IPC transport),
+// msx_schedule.cpp (the pure schedule functions), msx_engine.cpp (worker,
+// windows, copies), msx_rccl.cpp, msx_collectives.cpp, msx_rma.cpp and
+// msx_intercomm.cpp; what those share among themselves is in msx_engine.h.
+//
 // One process per GPU on one node.  Ranks find each other through a small TCP
 // hub (rank 0 listens on MASTER_ADDR:MSX_BOOTSTRAP_PORT), exchange HIP IPC
 // handles of the buffers a collective touches, and then every rank reads its
@@ -46,7 +51,7 @@ public:
     bool gpu_shared = false;
     // The engine's second stream belongs to the communicator, so collectives
     // of two communicators running at once from different threads never
-    // wait on each other (msx_transport.cpp, aux_stream).
+    // wait on each other (msx_engine.cpp, aux_stream).
     hipStream_t aux = nullptr;
     // lock-step host collectives over the bootstrap hub (all ranks, same n)
     virtual int allgather(const void* mine, size_t n, void* all) = 0;
@@ -123,7 +128,7 @@ int reduce_scatter_algo(int p, size_t total_count, int type_size, bool commutati
 int reduce_algo(int p, size_t count, int type_size, bool builtin);
 // allreduce Rabenseifner blocks: block j = [start, start+len), computed at newrank owner
 void allreduce_block(int p, size_t count, int j, size_t* start, size_t* len);
-// the pipelined two-step allreduce's chunk plan (msx_transport.cpp)
+// the pipelined two-step allreduce's chunk plan (msx_collectives.cpp)
 struct TwoStepRange { size_t e0, e1; int owner; };
 size_t two_step_chunk_el(int p, size_t esz);
 void two_step_plan(int p, size_t count, size_t pc_el, size_t ci, int me, std::vector<TwoStepRange>* ranges,

@@ -4,7 +4,7 @@ Every cross-rank wait in the engine is bounded (GPU flag waits by
 MSX_FLAG_TIMEOUT_MS, measured on the 100 MHz s_memrealtime clock inside the
 kernel; host barriers by MSX_BOOTSTRAP_TIMEOUT) and names what it waited for.
 MSX_TEST_DROP_FLAGS=<rank>:<seq> (test-only fault injection,
-msx_transport.cpp fault_drop_flags) makes <rank> skip its arrival-flag posts
+msx_engine.cpp fault_drop_flags) makes <rank> skip its arrival-flag posts
 of flag-synchronised call <seq>, so its peer's wait must run out.
 
 Two ranks share the box's GPU; the dropped call is a 4 KiB device allreduce

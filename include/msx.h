@@ -33,6 +33,21 @@
 #include <stdint.h>
 #include "mpi.h"
 
+/* 16-bit floating-point datatypes (extensions: MS-MPI predefines none, and
+ * mpi.h keeps MPI_REAL2 == MPI_DATATYPE_NULL).  Builtin-datatype handles in
+ * the 0x4c00SSII layout with size byte 02 and indices clear of mpi.h's (which
+ * end at 0x3d).  MSX_FLOAT16 is IEEE binary16, MSX_BFLOAT16 is bfloat16.
+ * Legal with MPI_MAX, MPI_MIN, MPI_SUM and MPI_PROD (every other builtin op:
+ * MPI_ERR_OP), with MPI_REPLACE / MPI_NO_OP in accumulates, with user ops, and
+ * as the base of any derived datatype.  SUM / PROD widen both operands exactly
+ * to fp32, do one IEEE fp32 operation and round the result to nearest-even
+ * (subnormals kept, overflow to inf); a NaN result follows the x86 rule of the
+ * fp32 path in the 16-bit format.  MAX / MIN return the chosen operand's bits
+ * (inout > in ? inout : in on the widened values).  Trees and collectives round
+ * at every combine. */
+#define MSX_FLOAT16         ((MPI_Datatype)0x4c000250)
+#define MSX_BFLOAT16        ((MPI_Datatype)0x4c000251)
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -29,6 +29,13 @@ struct loc_di { double v; int32_t l; int32_t pad; };
 struct loc_ff { float v; float l; };
 struct loc_dd { double v; double l; };
 static_assert(sizeof(loc_si) == 8 && sizeof(loc_di) == 16, "loc layout");
+// 16-bit floats (MSX_FLOAT16 = IEEE binary16, MSX_BFLOAT16; extensions, the
+// reference has neither): the raw bits, so MAX / MIN and the NaN rule return
+// an operand's bits untouched.
+struct f16 { uint16_t b; };
+struct bf16 { uint16_t b; };
+static_assert(sizeof(f16) == 2 && sizeof(bf16) == 2, "half layout");
+template <class T> struct is_half { static constexpr bool value = std::is_same<T, f16>::value || std::is_same<T, bf16>::value; };
 
 // ---- integer arithmetic with two's-complement wrap (MSVC semantics) -------
 template <class T> struct Wrap {
@@ -41,12 +48,53 @@ template <class T> struct Wrap {
 // ---- op functors: apply(inout, in) -> new inout ---------------------------
 template <int OP> struct Fn;
 
+// ---- 16-bit floats: widen exactly to fp32, one fp32 op, narrow -------------
+// widen() is exact.  narrow() rounds a non-NaN fp32 to nearest-even, produces
+// subnormals and overflows to +-inf: bf16 in integer form (the carry out of
+// the mantissa walks into the exponent, and 0x7F7F8000.. lands on 0x7F80),
+// fp16 with the round-to-nearest convert (v_cvt_f16_f32; the f16 denormal
+// mode is IEEE by default and is not touched by the f32 flag).
+__device__ __forceinline__ float widen(bf16 x) { return __uint_as_float((uint32_t)x.b << 16); }
+__device__ __forceinline__ float widen(f16 x) { return (float)__builtin_bit_cast(_Float16, x.b); }
+__device__ __forceinline__ void narrow(float r, bf16& o)
+{
+    const uint32_t u = __float_as_uint(r);
+    o.b = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+// The fp32 result is made opaque before the convert: left visible, hipcc fuses
+// `(half)(w(a) * w(b))` into v_fma_mixlo_f16 a, b, +0, whose +0 addend turns a
+// -0 product (x * -0, negative underflow) into +0.
+__device__ __forceinline__ void narrow(float r, f16& o)
+{
+    asm("" : "+v"(r));
+    o.b = __builtin_bit_cast(uint16_t, (_Float16)r);
+}
+__device__ __forceinline__ uint16_t qbit(f16) { return 0x0200; }
+__device__ __forceinline__ uint16_t qbit(bf16) { return 0x0040; }
+__device__ __forceinline__ uint16_t dnan16(f16) { return 0xFE00; }
+__device__ __forceinline__ uint16_t dnan16(bf16) { return 0xFFC0; }
+// r = w(io) op w(in) in fp32, already computed: n(r), or for a NaN r the x86
+// rule of x86nan below in the narrow format, `io` first.
+template <class H> __device__ __forceinline__ H half_result(float r, H io, H in, float wio, float win)
+{
+    H o;
+    if (__builtin_expect(r == r, 1)) { narrow(r, o); return o; }
+    o.b = (wio != wio) ? (uint16_t)(io.b | qbit(io)) : ((win != win) ? (uint16_t)(in.b | qbit(in)) : dnan16(io));
+    return o;
+}
+
 // Op<T>::Max/Min (op.cpp:18-40): minwindef.h max(inout,in) = inout>in?inout:in
+// (16-bit floats: the same rule on the widened values, the chosen operand's
+// bits returned unchanged)
 template <> struct Fn<O_MAX> {
     template <class T> __device__ static T apply(T io, T in) { return io > in ? io : in; }
+    __device__ static f16 apply(f16 io, f16 in) { return widen(io) > widen(in) ? io : in; }
+    __device__ static bf16 apply(bf16 io, bf16 in) { return widen(io) > widen(in) ? io : in; }
 };
 template <> struct Fn<O_MIN> {
     template <class T> __device__ static T apply(T io, T in) { return io < in ? io : in; }
+    __device__ static f16 apply(f16 io, f16 in) { return widen(io) < widen(in) ? io : in; }
+    __device__ static bf16 apply(bf16 io, bf16 in) { return widen(io) < widen(in) ? io : in; }
 };
 
 // ---- floating-point arithmetic with the reference platform's NaN rule ------
@@ -81,6 +129,12 @@ template <> struct Fn<O_SUM> {
     __device__ static double apply(double io, double in) { return fadd(io, in); }
     __device__ static c32 apply(c32 io, c32 in) { return c32{fadd(io.re, in.re), fadd(io.im, in.im)}; }
     __device__ static c64 apply(c64 io, c64 in) { return c64{fadd(io.re, in.re), fadd(io.im, in.im)}; }
+    template <class H>
+    __device__ static typename std::enable_if<is_half<H>::value, H>::type apply(H io, H in)
+    {
+        const float a = widen(io), b = widen(in);
+        return half_result(a + b, io, in, a, b);
+    }
 };
 
 // Op<T>::Prod (op.cpp:54-64) and complex *= (op.cpp:294-303): 4 mul + 2 add,
@@ -100,6 +154,12 @@ template <> struct Fn<O_PROD> {
     __device__ static double apply(double io, double in) { return fmul(io, in); }
     __device__ static c32 apply(c32 io, c32 in) { return cmul(io, in); }
     __device__ static c64 apply(c64 io, c64 in) { return cmul(io, in); }
+    template <class H>
+    __device__ static typename std::enable_if<is_half<H>::value, H>::type apply(H io, H in)
+    {
+        const float a = widen(io), b = widen(in);
+        return half_result(a * b, io, in, a, b);
+    }
 };
 
 // Op<T>::LogicalAnd/Or/Xor (op.cpp:66-124): C truthiness, stored as T(0/1).
@@ -147,18 +207,33 @@ template <> struct Fn<O_MINLOC> {
 };
 
 // ---- 16-byte vector apply ------------------------------------------------------
+// 16-bit floats: eight elements per vector, two per 32-bit lane (low half,
+// high half), repacked into the lane.
+template <int OP, class H>
+__device__ __forceinline__ uint32_t apply_half2(uint32_t io, uint32_t in)
+{
+    const H lo = Fn<OP>::apply(H{(uint16_t)io}, H{(uint16_t)in});
+    const H hi = Fn<OP>::apply(H{(uint16_t)(io >> 16)}, H{(uint16_t)(in >> 16)});
+    return (uint32_t)lo.b | ((uint32_t)hi.b << 16);
+}
+
 template <int OP, class VT>
 __device__ __forceinline__ u32x4 apply_vec(u32x4 io, u32x4 in)
 {
-    constexpr int N = 16 / (int)sizeof(VT);
-    VT a[N], b[N];
-    __builtin_memcpy(a, &io, 16);
-    __builtin_memcpy(b, &in, 16);
+    if constexpr (is_half<VT>::value) {
+        return u32x4{apply_half2<OP, VT>(io.x, in.x), apply_half2<OP, VT>(io.y, in.y),
+                     apply_half2<OP, VT>(io.z, in.z), apply_half2<OP, VT>(io.w, in.w)};
+    } else {
+        constexpr int N = 16 / (int)sizeof(VT);
+        VT a[N], b[N];
+        __builtin_memcpy(a, &io, 16);
+        __builtin_memcpy(b, &in, 16);
 #pragma unroll
-    for (int j = 0; j < N; ++j) a[j] = Fn<OP>::apply(a[j], b[j]);
-    u32x4 r;
-    __builtin_memcpy(&r, a, 16);
-    return r;
+        for (int j = 0; j < N; ++j) a[j] = Fn<OP>::apply(a[j], b[j]);
+        u32x4 r;
+        __builtin_memcpy(&r, a, 16);
+        return r;
+    }
 }
 
 template <bool NT>

@@ -372,6 +372,10 @@ hipError_t dispatch_arith(Kind k, const void* in, void* io, size_t n, hipStream_
     if constexpr (OP == O_LAND || OP == O_LOR || OP == O_LXOR) {
         if (k == K_BOOL) return run_default<OP, uint8_t>(in, io, n, s, c);
     }
+    if constexpr (OP == O_SUM || OP == O_PROD || OP == O_MAX || OP == O_MIN) {
+        if (k == K_F16) return run_default<OP, f16>(in, io, n, s, c);
+        if (k == K_BF16) return run_default<OP, bf16>(in, io, n, s, c);
+    }
     return hipErrorInvalidValue;
 }
 
@@ -473,6 +477,7 @@ hipError_t launch_tree_spec(int opidx, Kind k, const TreeSpec& t, void* out, siz
         if (t.src[0] == out) return hipSuccess;
         return hipMemcpyAsync(out, t.src[0], n * kind_size(k), hipMemcpyDeviceToDevice, s);   // xfer: device/pinned
     }
+    if (k == K_F16 || k == K_BF16) return tree_dispatch_half(opidx, k, a, ns, out, n, s);
     switch (opidx) {
     case O_SUM:    return tree_dispatch<O_SUM>(k, a, ns, out, n, s);
     case O_MAX:    return tree_dispatch<O_MAX>(k, a, ns, out, n, s);

@@ -402,6 +402,7 @@ hipError_t copy_g(int G, const CopyArgs& a, bool reg, hipStream_t s)
 template <int OP, class T> struct AccLegal {
     static constexpr bool arith = std::is_arithmetic<T>::value;
     static constexpr bool value =
+        ((OP == O_MAX || OP == O_MIN || OP == O_SUM || OP == O_PROD) && is_half<T>::value) ||
         ((OP == O_MAX || OP == O_MIN || OP == O_LAND || OP == O_LOR || OP == O_LXOR) && arith) ||
         ((OP == O_SUM || OP == O_PROD) && (arith || std::is_same<T, c32>::value || std::is_same<T, c64>::value)) ||
         ((OP == O_BAND || OP == O_BOR || OP == O_BXOR) && std::is_integral<T>::value) ||
@@ -457,6 +458,8 @@ hipError_t acc_kind(Kind k, const DevLayout& L, int64_t count, const void* packe
     case K_LOC_DI: return run_acc<OP, loc_di>(L, count, packed, typed, s);
     case K_LOC_FF: return run_acc<OP, loc_ff>(L, count, packed, typed, s);
     case K_LOC_DD: return run_acc<OP, loc_dd>(L, count, packed, typed, s);
+    case K_F16: return run_acc<OP, f16>(L, count, packed, typed, s);
+    case K_BF16: return run_acc<OP, bf16>(L, count, packed, typed, s);
     default: return hipErrorInvalidValue;
     }
 }

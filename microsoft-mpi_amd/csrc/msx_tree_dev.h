@@ -465,5 +465,9 @@ __global__ __launch_bounds__(BLOCK) void k_tree(TreeArgs a, T* __restrict__ out,
 constexpr size_t kTreeNtMin = (size_t)256 << 20;
 template <int OP>
 hipError_t tree_dispatch(Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n, hipStream_t s);
+// K_F16 / K_BF16 under MAX, MIN, SUM, PROD: a translation unit of their own
+// (msx_tree_half.hip), so the per-op units' compile time does not grow
+hipError_t tree_dispatch_half(int opidx, Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n,
+                              hipStream_t s);
 
 }  // namespace msx

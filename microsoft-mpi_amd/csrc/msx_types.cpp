@@ -72,6 +72,9 @@ const TypeInfo kTypes[] = {
     {MPI_LONG_DOUBLE_INT,    K_LOC_DI, G_LOC, 16, "MPI_LONG_DOUBLE_INT"},
     {MPI_2REAL,              K_LOC_FF, G_LOC, 8,  "MPI_2REAL"},
     {MPI_2DOUBLE_PRECISION,  K_LOC_DD, G_LOC, 16, "MPI_2DOUBLE_PRECISION"},
+    // 16-bit floats: extensions declared in msx.h (the reference has none)
+    {MSX_FLOAT16,            K_F16,  G_HALF, 2, "MSX_FLOAT16"},
+    {MSX_BFLOAT16,           K_BF16, G_HALF, 2, "MSX_BFLOAT16"},
 };
 
 }  // namespace
@@ -101,7 +104,7 @@ int kind_size(Kind k)
 {
     switch (k) {
     case K_I8: case K_U8: case K_BOOL: return 1;
-    case K_I16: case K_U16: return 2;
+    case K_I16: case K_U16: case K_F16: case K_BF16: return 2;
     case K_I32: case K_U32: case K_F32: return 4;
     case K_I64: case K_U64: case K_F64: case K_C32:
     case K_LOC_II: case K_LOC_FI: case K_LOC_SI: case K_LOC_FF: return 8;
@@ -114,9 +117,9 @@ int op_legal_groups(int opidx)
 {
     switch (opidx) {
     case O_MAX: case O_MIN:                 // op.cpp:1449-1521
-        return G_CINT | G_FINT | G_FLOAT | G_PCHAR;
+        return G_CINT | G_FINT | G_FLOAT | G_PCHAR | G_HALF;
     case O_SUM: case O_PROD:                // op.cpp:1680-1883
-        return G_CINT | G_FINT | G_FLOAT | G_COMPLEX | G_PCHAR;
+        return G_CINT | G_FINT | G_FLOAT | G_COMPLEX | G_PCHAR | G_HALF;
     case O_LAND: case O_LOR: case O_LXOR:   // op.cpp:1026-1386
         return G_CINT | G_FINT | G_LOGICAL | G_CBOOL | G_FLOAT | G_PCHAR;
     case O_BAND: case O_BOR: case O_BXOR:   // op.cpp:739-1002

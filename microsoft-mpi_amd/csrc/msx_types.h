@@ -11,6 +11,7 @@
 
 #include <stdint.h>
 #include "../../include/mpi.h"
+#include "../../include/msx.h"   // MSX_FLOAT16, MSX_BFLOAT16
 
 namespace msx {
 
@@ -21,6 +22,7 @@ enum Kind : int {
     K_I8, K_U8, K_I16, K_U16, K_I32, K_U32, K_I64, K_U64,
     K_F32, K_F64, K_BOOL, K_C32, K_C64,
     K_LOC_II, K_LOC_FI, K_LOC_SI, K_LOC_DI, K_LOC_FF, K_LOC_DD,
+    K_F16, K_BF16,     // MSX_FLOAT16 / MSX_BFLOAT16 (msx.h): not in the reference
     K_COUNT
 };
 
@@ -41,7 +43,11 @@ constexpr int OBJ_OP = 6;
 // Legality groups of the check tables.
 enum Group : int {
     G_CINT = 1, G_FINT = 2, G_FLOAT = 4, G_COMPLEX = 8, G_LOGICAL = 16,
-    G_CBOOL = 32, G_BYTE = 64, G_PCHAR = 128, G_LOC = 256
+    G_CBOOL = 32, G_BYTE = 64, G_PCHAR = 128, G_LOC = 256,
+    // 16-bit floats (extensions): MAX, MIN, SUM, PROD only.  The non-strict
+    // tables' LAND/LOR/LXOR on floats are a quirk of the reference's own types
+    // and are not extended to types it does not have.
+    G_HALF = 512
 };
 
 struct TypeInfo {

@@ -21,10 +21,13 @@ INCLUDE_DIR = os.path.join(REPO_ROOT, "include")
 _lib = None
 
 
-def _parse_header_constants(path):
-    """#define NAME value / ((T)0x...) from include/mpi.h -> dict (ints only)."""
+def _parse_header_constants(path, prefix="MPI"):
+    """#define NAME value / ((T)0x...) from include/mpi.h -> dict (ints only).
+
+    `prefix` selects the names: MPI_* from mpi.h, MSX_* (the extension
+    datatypes MSX_FLOAT16 / MSX_BFLOAT16) from msx.h."""
     out = {}
-    pat = re.compile(r"^#define\s+(MPI_\w+)\s+(.+?)\s*(?:/\*.*)?$")
+    pat = re.compile(r"^#define\s+(%s_\w+)\s+(.+?)\s*(?:/\*.*)?$" % prefix)
     enum = re.compile(r"^(MPI_\w+)\s*=\s*(\d+),?$")
     with open(path) as f:
         for line in f:
@@ -46,7 +49,8 @@ def _parse_header_constants(path):
     return out
 
 
-C = SimpleNamespace(**_parse_header_constants(os.path.join(INCLUDE_DIR, "mpi.h")))
+C = SimpleNamespace(**_parse_header_constants(os.path.join(INCLUDE_DIR, "mpi.h")),
+                    **_parse_header_constants(os.path.join(INCLUDE_DIR, "msx.h"), "MSX"))
 
 
 def _signed32(v):

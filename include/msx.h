@@ -126,6 +126,31 @@ void msx_op_errno_reset(void);
 int msx_reduce_local_dev(const void* in, void* inout, int64_t count,
                          MPI_Datatype datatype, MPI_Op op, void* stream);
 
+/* Device-resident user-defined reduction ops.
+ *
+ * A device user function: inout[i] = in[i] (op) inout[i] for i in [0,count),
+ * MPI's operand order (`in` is the left operand), done by ENQUEUEING work on
+ * `stream` (a hipStream_t).  in/inout are device-accessible.  For a derived
+ * datatype they are the typed base addresses of `count` instances, as an
+ * MPI_User_function gets them.  The function must not synchronise the stream
+ * or the device and must not call MPI.  It may run on a library thread (the
+ * engine worker, for non-blocking calls).  Returns MPI_SUCCESS or an MPI
+ * error class, which fails the calling MPI call with that class.
+ * include/msx_device_op.h is a kernel kit for writing one.
+ *
+ * msx_op_create_device returns a user-op handle (MPI_Op_commutative and
+ * MPI_Op_free apply) that MPI_Reduce_local, msx_reduce_local_dev, MPI_Reduce,
+ * MPI_Allreduce, MPI_Reduce_scatter[_block], MPI_Scan, MPI_Exscan and their
+ * non-blocking forms accept; host buffers are staged to the GPU around the
+ * calls.  Each collective evaluates the order of the host user-op path.
+ * One-sided calls and intercommunicator reductions return MPI_ERR_OP; without
+ * a GPU every use fails with MPI_ERR_OTHER and the function is never called. */
+typedef int (MSX_Device_function)(const void* in, void* inout, int64_t count,
+                                  MPI_Datatype datatype, void* stream, void* state);
+int msx_op_create_device(MSX_Device_function* fn, int commute, void* state, MPI_Op* op);
+/* 1 device op, 0 any other valid op, -1 invalid */
+int msx_op_is_device(MPI_Op op);
+
 /* packed[i*size + b] <- typed[i*extent + map(b)] for `count` instances of a
  * committed datatype (predefined or derived); typed is the buffer address the
  * type map is relative to.  Device pointers, stream-ordered. */

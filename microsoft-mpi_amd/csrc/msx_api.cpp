@@ -46,6 +46,8 @@ struct UserOp {
     MPI_User_function* fn = nullptr;
     bool commute = true;
     bool live = false;
+    MSX_Device_function* dev_fn = nullptr;   // msx_op_create_device: fn is null
+    void* dev_state = nullptr;
 };
 std::mutex g_op_mu;
 std::vector<UserOp> g_user_ops;
@@ -201,6 +203,8 @@ int v_op_handle(MPI_Op op, OpRef* out)
         }
         out->opidx = idx;
         out->user_fn = nullptr;
+        out->dev_fn = nullptr;
+        out->dev_state = nullptr;
         out->commutative = (idx != O_REPLACE && idx != O_NOOP);
         return MPI_SUCCESS;
     }
@@ -212,7 +216,19 @@ int v_op_handle(MPI_Op op, OpRef* out)
     }
     out->opidx = O_NULL;
     out->user_fn = g_user_ops[idx].fn;
+    out->dev_fn = g_user_ops[idx].dev_fn;
+    out->dev_state = g_user_ops[idx].dev_state;
     out->commutative = g_user_ops[idx].commute;
+    return MPI_SUCCESS;
+}
+
+// Intercommunicator reductions are a frozen layer: no device user ops there.
+int v_no_device_op_inter(const Comm* c, const OpRef& r)
+{
+    if (c->inter && r.dev_fn) {
+        set_error("device user ops are not supported on intercommunicators");
+        return MPI_ERR_OP;
+    }
     return MPI_SUCCESS;
 }
 
@@ -665,9 +681,32 @@ MSX_EXPORT int MPI_Op_create(MPI_User_function* user_fn, int commute, MPI_Op* op
     size_t idx = 0;
     while (idx < g_user_ops.size() && g_user_ops[idx].live) ++idx;
     if (idx == g_user_ops.size()) g_user_ops.push_back(UserOp{});
-    g_user_ops[idx] = UserOp{user_fn, commute != 0, true};
+    g_user_ops[idx] = UserOp{user_fn, commute != 0, true, nullptr, nullptr};
     *op = kUserOpBase | (int)idx;
     return MPI_SUCCESS;
+}
+
+// A user op whose function enqueues its combine on a HIP stream (msx.h): the
+// same MPID_Op pool and handle layout as MPI_Op_create.
+MSX_EXPORT int msx_op_create_device(MSX_Device_function* fn, int commute, void* state, MPI_Op* op)
+{
+    MSX_REQUIRE_INIT("msx_op_create_device");
+    if (fn == nullptr) { set_error("null device function"); return MPI_ERR_ARG; }
+    if (op == nullptr) { set_error("null op"); return MPI_ERR_ARG; }
+    std::lock_guard<std::mutex> g(g_op_mu);
+    size_t idx = 0;
+    while (idx < g_user_ops.size() && g_user_ops[idx].live) ++idx;
+    if (idx == g_user_ops.size()) g_user_ops.push_back(UserOp{});
+    g_user_ops[idx] = UserOp{nullptr, commute != 0, true, fn, state};
+    *op = kUserOpBase | (int)idx;
+    return MPI_SUCCESS;
+}
+
+MSX_EXPORT int msx_op_is_device(MPI_Op op)
+{
+    OpRef r;
+    if (v_op_handle(op, &r) != MPI_SUCCESS) return -1;
+    return r.dev_fn ? 1 : 0;
 }
 
 MSX_EXPORT int MPI_Op_free(MPI_Op* op)
@@ -757,12 +796,14 @@ int v_reduce(Comm* c, const void* sendbuf, void* recvbuf, int count, MPI_Datatyp
         if (root == MPI_PROC_NULL) { *skip = true; return MPI_SUCCESS; }
         if (root == MPI_ROOT) {
             int rc = v_dtype_any(recvbuf, count, datatype);
-            return rc == MPI_SUCCESS ? v_op(op, datatype, r) : rc;
+            if (rc == MPI_SUCCESS) rc = v_op(op, datatype, r);
+            return rc == MPI_SUCCESS ? v_no_device_op_inter(c, *r) : rc;
         }
         if (root < 0 || root >= (int)c->remote_lpid.size()) { set_error("invalid root %d", root); return MPI_ERR_ROOT; }
         if (count > 0 && sendbuf == MPI_IN_PLACE) { set_error("**sendbuf_inplace"); return MPI_ERR_BUFFER; }
         int rc = v_dtype_any(sendbuf, count, datatype);
-        return rc == MPI_SUCCESS ? v_op(op, datatype, r) : rc;
+        if (rc == MPI_SUCCESS) rc = v_op(op, datatype, r);
+        return rc == MPI_SUCCESS ? v_no_device_op_inter(c, *r) : rc;
     }
     if (root < 0 || root >= c->size) { set_error("invalid root %d", root); return MPI_ERR_ROOT; }
     int rc = v_dtype_any(sendbuf, count, datatype);
@@ -805,6 +846,7 @@ MSX_EXPORT int MPI_Allreduce(const void* sendbuf, void* recvbuf, int count, MPI_
     int rc = v_comm(comm, &c);
     if (rc == MPI_SUCCESS) rc = v_dtype_any(recvbuf, count, datatype);
     if (rc == MPI_SUCCESS) rc = v_op(op, datatype, &r);
+    if (rc == MPI_SUCCESS) rc = v_no_device_op_inter(c, r);
     if (rc == MPI_SUCCESS && count > 0) rc = v_allreduce_bufs(c, sendbuf, recvbuf, count, datatype);
     if (rc == MPI_SUCCESS && count > 0)
         rc = c->inter ? engine_inter_allreduce(c, sendbuf, recvbuf, (size_t)count, datatype, r)
@@ -838,6 +880,7 @@ int validate_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const i
     }
     int rc = v_dtype_any(sendbuf, sentinel, datatype);
     if (rc == MPI_SUCCESS) rc = v_op(op, datatype, r);
+    if (rc == MPI_SUCCESS) rc = v_no_device_op_inter(c, *r);
     if (rc == MPI_SUCCESS && recvcounts[c->rank] > 0) {
         if (recvbuf == MPI_IN_PLACE) { set_error("recvbuf is MPI_IN_PLACE"); rc = MPI_ERR_BUFFER; }
         else if (sendbuf != MPI_IN_PLACE) {
@@ -959,6 +1002,7 @@ MSX_EXPORT int MPI_Iallreduce(const void* sendbuf, void* recvbuf, int count, MPI
     if (rc == MPI_SUCCESS) *request = MPI_REQUEST_NULL;
     if (rc == MPI_SUCCESS) rc = v_dtype_any(recvbuf, count, datatype);
     if (rc == MPI_SUCCESS) rc = v_op(op, datatype, &r);
+    if (rc == MPI_SUCCESS) rc = v_no_device_op_inter(c, r);
     if (rc == MPI_SUCCESS && count > 0) rc = v_allreduce_bufs(c, sendbuf, recvbuf, count, datatype);
     if (rc == MPI_SUCCESS && c->inter) {
         const size_t n = (size_t)count;
@@ -2407,13 +2451,18 @@ MSX_EXPORT int msx_reduce_local_dev(const void* in, void* inout, int64_t count, 
     OpRef r;
     int rc = v_op(op, dt, &r);
     if (rc != MPI_SUCCESS) return rc;
-    if (r.opidx == O_NULL) { set_error("device entry point takes builtin ops only"); return MPI_ERR_OP; }
+    if (r.opidx == O_NULL && !r.dev_fn) {
+        set_error("device entry point takes builtin ops and device user ops only");
+        return MPI_ERR_OP;
+    }
     if (count < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
     if (!in || !inout) { set_error("null buffer"); return MPI_ERR_BUFFER; }
     if (in == inout) { set_error("inbuf aliases inoutbuf"); return MPI_ERR_BUFFER; }
     rc = ensure_device();
     if (rc != MPI_SUCCESS) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the HIP null stream
+    // a device user op: its own launch on the caller's stream, enqueue only
+    if (r.dev_fn) return device_op_call(r, dt, in, inout, (size_t)count, s);
     return reduce_local_device(r.opidx, type_info(dt)->kind, in, inout, (size_t)count, s);
 }
 

@@ -52,7 +52,9 @@ void two_step_plan(int p, size_t count, size_t pc_el, size_t ci, int me, std::ve
 int do_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
                  const OpRef& op, int root, bool nbc)
 {
-    // user functions are host code: no GPU needed on this path
+    // device user ops stay in HBM (msx_devop.cpp); MPI_Op_create's functions
+    // are host code: no GPU needed on that path
+    if (op.dev_fn) return devop_allreduce(c, sendbuf, recvbuf, count, dt, op);
     if (op.opidx == O_NULL) return host_user_allreduce(c, sendbuf, recvbuf, count, dt, op);
     int rc = ensure_device();
     if (rc != MPI_SUCCESS) return rc;
@@ -416,6 +418,7 @@ namespace {
 int do_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const int* recvcounts,
                       MPI_Datatype dt, const OpRef& op)
 {
+    if (op.dev_fn) return devop_reduce_scatter(c, sendbuf, recvbuf, recvcounts, dt, op);
     Transport* tp = c->tp;
     const int p = c->size, me = c->rank;
     const size_t esz = dtype_is_derived(dt) ? 0 : (size_t)type_size(dt);   // derived: user ops only
@@ -686,6 +689,7 @@ int engine_reduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI
     // Builtin ops: the reference's binomial / Rabenseifner trees (do_allreduce
     // in reduce mode); user ops: host_user_reduce.
     return worker().run([=]() -> int {
+        if (op.dev_fn) return devop_reduce(c, sendbuf, recvbuf, count, dt, op, root);
         if (op.opidx == O_NULL) return host_user_reduce(c, sendbuf, recvbuf, count, dt, op, root);
         return do_allreduce(c, sendbuf, recvbuf, count, dt, op, root, nbc);
     });
@@ -759,6 +763,7 @@ int combine2(int opidx, Kind k, const char* inout_src, const char* in, char* out
 int do_scan(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
             const OpRef& op, bool exclusive)
 {
+    if (op.dev_fn) return devop_scan(c, sendbuf, recvbuf, count, dt, op, exclusive);
     if (op.opidx == O_NULL) return host_user_scan(c, sendbuf, recvbuf, count, dt, op, exclusive);
     int rc = ensure_device();
     if (rc != MPI_SUCCESS) return rc;

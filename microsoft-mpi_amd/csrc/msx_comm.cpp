@@ -177,9 +177,96 @@ int local_combine_typed(const OpRef& op, MPI_Datatype dt, const void* in, void* 
     return rc;
 }
 
+// MSX_Device_function contract (msx.h): enqueue only; its error class is ours.
+int device_op_call(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count, hipStream_t s)
+{
+    const int rc = op.dev_fn(in, inout, (int64_t)count, dt, static_cast<void*>(s), op.dev_state);
+    if (rc != MPI_SUCCESS) set_error("device user function returned error class %d", rc);
+    return rc;
+}
+
+namespace {
+
+// HBM staging of host operands for device user ops (grows, never shrinks);
+// one caller at a time.
+struct DevOpStage {
+    std::mutex mu;
+    char* p[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    char* get(int i, size_t bytes)
+    {
+        if (bytes > cap[i]) {
+            if (p[i]) (void)hipFree(p[i]);
+            p[i] = nullptr;
+            cap[i] = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&p[i]), bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return nullptr;
+            }
+            cap[i] = bytes;
+        }
+        return p[i];
+    }
+};
+DevOpStage g_devop_stage;
+
+// MPI_Reduce_local with a device user op.  Device operands: one call of the
+// function on the library's stream with the caller's pointers and the whole
+// count, one sync, no staging.  A host operand is staged through HBM over the
+// byte span its type map touches (the mirror image of local_combine_typed), so
+// the function sees device memory only and the gap bytes of a derived `inout`
+// come back unchanged.
+int local_combine_device(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count)
+{
+    int rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;     // no GPU: MPI_ERR_OTHER, the function is never called
+    int64_t lo = 0, hi = 0;
+    if (dtype_is_derived(dt)) {
+        const Dtype* t = dtype_lookup(dt);
+        if (!t) { set_error("invalid datatype 0x%x", dt); return MPI_ERR_TYPE; }
+        dt_span(t, (int64_t)count, &lo, &hi);
+    } else {
+        const int esz = type_size(dt);
+        if (esz <= 0) { set_error("datatype 0x%x not supported with user ops", dt); return MPI_ERR_TYPE; }
+        hi = (int64_t)(count * (size_t)esz);
+    }
+    const size_t span = (size_t)(hi - lo);
+    const char* pin = static_cast<const char*>(in);
+    char* pio = static_cast<char*>(inout);
+    const BufInfo bi = classify(pin + lo), bo = classify(pio + lo);
+    hipStream_t s = internal_stream();
+    const bool in_dev = bi.place == Place::Device, io_dev = bo.place == Place::Device;
+    std::unique_lock<std::mutex> g(g_devop_stage.mu, std::defer_lock);
+    if (span && !(in_dev && io_dev)) {
+        g.lock();
+        const size_t room = (span + 255) & ~(size_t)255;
+        if (!in_dev) {
+            char* d = g_devop_stage.get(0, room);
+            if (!d) { set_error("device user op: staging allocation failed"); return MPI_ERR_NO_MEM; }
+            if ((rc = copy_any(d, pin + lo, span)) != MPI_SUCCESS) return rc;
+            pin = d - lo;
+        }
+        if (!io_dev) {
+            char* d = g_devop_stage.get(1, room);
+            if (!d) { set_error("device user op: staging allocation failed"); return MPI_ERR_NO_MEM; }
+            if ((rc = copy_any(d, pio + lo, span)) != MPI_SUCCESS) return rc;
+            pio = d - lo;
+        }
+    }
+    rc = device_op_call(op, dt, pin, pio, count, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc != MPI_SUCCESS) return rc;
+    if (e != hipSuccess) return hip_fail(e, "device user op");
+    if (span && !io_dev) rc = copy_any(static_cast<char*>(inout) + lo, pio + lo, span);
+    return rc;
+}
+
+}  // namespace
+
 int local_combine(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count)
 {
     if (count == 0) return MPI_SUCCESS;
+    if (op.dev_fn) return local_combine_device(op, dt, in, inout, count);
     if (op.opidx != O_NULL) {
         const TypeInfo* t = type_info(dt);
         if (!t) { set_error("datatype 0x%x has no reduction kernel", dt); return MPI_ERR_OP; }

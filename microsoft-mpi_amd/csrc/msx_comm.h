@@ -50,6 +50,10 @@ struct OpRef {
     int opidx = O_NULL;                 // builtin index, or O_NULL for user ops
     MPI_User_function* user_fn = nullptr;
     bool commutative = true;
+    // device-resident user op (msx_op_create_device): opidx == O_NULL, user_fn
+    // null; dev_fn enqueues the combine on a stream and gets `dev_state`
+    MSX_Device_function* dev_fn = nullptr;
+    void* dev_state = nullptr;
 };
 
 // MSMPI_FORCE_ASYNC_WORKFLOW (mpid/env.cpp:1381-1384, read at MPI_Init with
@@ -79,8 +83,12 @@ int coll_scan(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Dat
               const OpRef& op, bool exclusive);
 int coll_barrier(Comm* c);
 
-// Local combine with any op (builtin -> GPU kernel; user fn -> host call).
+// Local combine with any op (builtin -> GPU kernel; user fn -> host call;
+// device user fn -> its own launch on device-accessible operands).
 int local_combine(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count);
+// One call of a device user function on `s` with typed bases (enqueue only);
+// the function's error class fails the caller.
+int device_op_call(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count, hipStream_t s);
 
 // Copy `bytes` between any two buffers (host or device), blocking.
 int copy_any(void* dst, const void* src, size_t bytes);

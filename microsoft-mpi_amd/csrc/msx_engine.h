@@ -6,6 +6,7 @@
 //   msx_engine.cpp       worker thread, window geometry, copies, user-op host path
 //   msx_rccl.cpp         RCCL loader and both RCCL planes
 //   msx_collectives.cpp  allreduce / reduce / reduce_scatter / scan schedules
+//   msx_devop.cpp        the same collectives with a device-resident user op
 //   msx_rma.cpp          fence, passive-target and PSCW one-sided operations
 //   msx_intercomm.cpp    world mailbox, intercommunicators, communicator split / free
 // Never included by msx_api.cpp, msx_comm.cpp or a .hip unit: they see the
@@ -278,6 +279,18 @@ int do_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_
                  const OpRef& op, int root = -1, bool nbc = false);
 int host_user_reduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
                      const OpRef& op, int root);
+
+// ---- msx_devop.cpp ----------------------------------------------------------
+// The reduction collectives with a device user op (op.dev_fn): a device gather
+// over the windows, then the host user-op path's order evaluated in device
+// scratch with the user's launches.  Engine worker (or the inline blocking call).
+int devop_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt, const OpRef& op);
+int devop_reduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt, const OpRef& op,
+                 int root);
+int devop_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const int* recvcounts, MPI_Datatype dt,
+                         const OpRef& op);
+int devop_scan(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt, const OpRef& op,
+               bool exclusive);
 
 // ---- msx_rma.cpp ------------------------------------------------------------
 void futex_wake_all(void* addr);

@@ -184,6 +184,33 @@ int msx_reduce_tree_spec_dev(const void* const* srcs, int P, unsigned pairmask, 
 /* The engine's local copy kernel (the collectives' collect step): dst <- src,
  * `bytes` bytes of device memory, stream-ordered (tests of the copy kernels). */
 int msx_copy_dev(void* dst, const void* src, int64_t bytes, void* stream);
+/* Tests of the engine's kernels in the launch forms only a collective uses.
+ * Every pointer is device memory of the caller; the library allocates and
+ * frees nothing.  Bad arguments (null arrays, nextra outside 0..31, nflags
+ * outside 0..64, done_launches < 1 with a counter, a negative size, nseg
+ * outside 0..32 for the push) return MPI_ERR_ARG before any GPU is touched.
+ *
+ * msx_reduce_tree_done_dev: msx_reduce_tree_spec_dev whose result also goes to
+ * extra[0..nextra) and, with done_counter (a zeroed block of 1024 unsigned
+ * words, left zero), is stored write-through and announced: once the
+ * workgroups of `done_launches` launches on the block (this one included,
+ * stream-ordered) have stored, done_seq is stored to every done_flags[i].
+ * count == 0 launches nothing and counts no launch.
+ * msx_push_dev: the GPU-flag schedules' push: segment i (below 4 GiB) to
+ * dst[i] with write-through stores, then `seq` to every flags[i]; nseg == 0
+ * posts the flags alone.  `counter` as above.  The launch's waiting workgroup
+ * waits for nothing; wait_flags and wait_err name one device word each.
+ * msx_copy_segs_dev: the engine's multi-segment copy, any nseg >= 0. */
+int msx_reduce_tree_done_dev(const void* const* srcs, int P, unsigned pairmask, int nleaves, int chain,
+                             void* out, void* const* extra, int nextra, unsigned* done_counter,
+                             int done_launches, unsigned long long* const* done_flags, int done_nflags,
+                             unsigned long long done_seq, int64_t count, MPI_Datatype datatype, MPI_Op op,
+                             void* stream);
+int msx_push_dev(const void* const* src, void* const* dst, const int64_t* nbytes, int nseg,
+                 unsigned long long* const* flags, int nflags, unsigned long long seq, unsigned* counter,
+                 const unsigned long long* wait_flags, int* wait_err, void* stream);
+int msx_copy_segs_dev(const void* const* src, void* const* dst, const int64_t* nbytes, int nseg,
+                      void* stream);
 /* Test hook: pack / unpack geometry.  0 = by size (default: the one-wave tile
  * form when typed span + packed bytes exceed 512 MiB), 1 = always the
  * grid-stride form, 2 = always the tile form.  (The derived-target accumulate
@@ -206,7 +233,9 @@ int msx_set_host_mode(int mode);
  * which = 0 allreduce tree of newrank n, 1 reduce_scatter tree of newrank n,
  * 2 pairwise chain of real rank n, 3 MPI_Reduce Rabenseifner tree of newrank n,
  * 4 MPI_Reduce binomial tree for root n.  src32[i] = real rank in kernel slot
- * i (-1 = empty). */
+ * i (-1 = empty).  The kernels' 16 leaves admit p <= 31 for the fold trees
+ * (which = 0, 1, 3) and p <= 16 for the chain and the binomial tree; a larger
+ * p is MPI_ERR_ARG. */
 int msx_schedule_tree(int which, int p, int n, int* src32, int* P, unsigned* pairmask,
                       int* chain);
 /* which = 0 allreduce, 1 reduce_scatter, 2 reduce: 0 recursive doubling,

@@ -2553,6 +2553,122 @@ MSX_EXPORT int msx_copy_dev(void* dst, const void* src, int64_t bytes, void* str
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "copy kernel launch");
 }
 
+// msx_reduce_tree_spec_dev plus the TreeSpec fields only a collective sets
+// (extra destinations, the result-ready count and its flags), so the tree
+// kernels' write-through stores and tree_done run outside a collective.  Every
+// pointer is the caller's device memory; nothing is allocated or freed here.
+MSX_EXPORT int msx_reduce_tree_done_dev(const void* const* srcs, int P, unsigned pairmask, int nleaves, int chain,
+                                        void* out, void* const* extra, int nextra, unsigned* done_counter,
+                                        int done_launches, unsigned long long* const* done_flags, int done_nflags,
+                                        unsigned long long done_seq, int64_t count, MPI_Datatype dt, MPI_Op op,
+                                        void* stream)
+{
+    OpRef r;
+    int rc = v_op(op, dt, &r);
+    if (rc != MPI_SUCCESS) return rc;
+    if (r.opidx == O_NULL) { set_error("device entry point takes builtin ops only"); return MPI_ERR_OP; }
+    const bool pow2 = P >= 1 && P <= 16 && (P & (P - 1)) == 0;
+    if (count < 0 || !srcs || !out || (chain ? (P < 1 || P > 16) : !pow2) || nleaves < 0 || nleaves > P ||
+        (!chain && (pairmask >> P) != 0)) {
+        set_error("bad tree spec (P=%d pairmask=0x%x nleaves=%d chain=%d count=%lld)", P, pairmask, nleaves, chain,
+                  (long long)count);
+        return MPI_ERR_ARG;
+    }
+    if (nextra < 0 || nextra > 31 || (nextra > 0 && !extra)) {
+        set_error("bad extra destinations (nextra=%d)", nextra);
+        return MPI_ERR_ARG;
+    }
+    for (int e = 0; e < nextra; ++e)
+        if (!extra[e]) { set_error("null extra destination %d", e); return MPI_ERR_ARG; }
+    if (done_nflags < 0 || done_nflags > 64 || (done_nflags > 0 && (!done_flags || !done_counter)) ||
+        (done_counter && done_launches < 1)) {
+        set_error("bad result-ready count (nflags=%d launches=%d)", done_nflags, done_launches);
+        return MPI_ERR_ARG;
+    }
+    for (int i = 0; i < done_nflags; ++i)
+        if (!done_flags[i]) { set_error("null result-ready flag %d", i); return MPI_ERR_ARG; }
+    if (count == 0) return MPI_SUCCESS;
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    TreeSpec t;
+    t.P = P;
+    t.chain = chain != 0;
+    t.pairmask = chain ? 0 : pairmask;
+    t.nleaves = chain ? 0 : nleaves;
+    const int ns = chain ? P : 2 * P;
+    for (int i = 0; i < ns; ++i) t.src[i] = srcs[i];
+    t.nextra = nextra;
+    for (int e = 0; e < nextra; ++e) t.extra[e] = extra[e];
+    if (done_counter) {
+        t.done_counter = done_counter;
+        t.done_launches = (unsigned)done_launches;
+        t.done_nflags = done_nflags;
+        for (int i = 0; i < done_nflags; ++i) t.done_flags[i] = done_flags[i];
+        t.done_seq = done_seq;
+    }
+    hipError_t e = launch_tree_spec(r.opidx, type_info(dt)->kind, t, out, (size_t)count, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "tree kernel launch");
+}
+
+namespace {
+// (src, dst, nbytes) triples of the two segment hooks: arrays present, sizes
+// not negative, a pointer for every non-empty segment
+int v_segs(const void* const* src, void* const* dst, const int64_t* nbytes, int nseg, std::vector<size_t>* nb)
+{
+    if (nseg > 0 && (!src || !dst || !nbytes)) { set_error("null segment array"); return MPI_ERR_ARG; }
+    nb->resize((size_t)nseg);
+    for (int i = 0; i < nseg; ++i) {
+        if (nbytes[i] < 0 || (nbytes[i] > 0 && (!src[i] || !dst[i]))) {
+            set_error("bad segment %d (%lld bytes)", i, (long long)nbytes[i]);
+            return MPI_ERR_ARG;
+        }
+        (*nb)[(size_t)i] = (size_t)nbytes[i];
+    }
+    return MPI_SUCCESS;
+}
+}  // namespace
+
+// The push of the GPU-flag schedules (k_push_wait) over the caller's segments,
+// flags and counter block (kCountWords zeroed words, left zero).  The launch's
+// waiting workgroup is given no flag to wait for (wait_n = 0): it only reads
+// *wait_flags once and never writes *wait_err, which must both be device words.
+MSX_EXPORT int msx_push_dev(const void* const* src, void* const* dst, const int64_t* nbytes, int nseg,
+                            unsigned long long* const* flags, int nflags, unsigned long long seq, unsigned* counter,
+                            const unsigned long long* wait_flags, int* wait_err, void* stream)
+{
+    if (nseg < 0 || nseg > 32) { set_error("push takes 0..32 segments (nseg=%d)", nseg); return MPI_ERR_ARG; }
+    std::vector<size_t> nb;
+    int rc = v_segs(src, dst, nbytes, nseg, &nb);
+    if (rc != MPI_SUCCESS) return rc;
+    if (nflags < 0 || nflags > 64 || (nflags > 0 && !flags) || (nseg > 0 && !counter) || !wait_flags || !wait_err) {
+        set_error("bad push flags (nflags=%d)", nflags);
+        return MPI_ERR_ARG;
+    }
+    for (int i = 0; i < nflags; ++i)
+        if (!flags[i]) { set_error("null flag %d", i); return MPI_ERR_ARG; }
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    hipError_t e = launch_push_wait(src, dst, nb.data(), nseg, flags, nflags, seq, counter, wait_flags, 0, -1, wait_err,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "push kernel launch");
+}
+
+// The engine's multi-segment copy (k_copy_segs, the collect of allgather
+// blocks): any number of segments, batched by the launcher.
+MSX_EXPORT int msx_copy_segs_dev(const void* const* src, void* const* dst, const int64_t* nbytes, int nseg,
+                                 void* stream)
+{
+    if (nseg < 0) { set_error("negative segment count"); return MPI_ERR_ARG; }
+    std::vector<size_t> nb;
+    int rc = v_segs(src, dst, nbytes, nseg, &nb);
+    if (rc != MPI_SUCCESS) return rc;
+    if (nseg == 0) return MPI_SUCCESS;
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    hipError_t e = launch_copy_segs(src, dst, nb.data(), nseg, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "copy kernel launch");
+}
+
 // Test hook: the pack/unpack/accumulate kernel geometry (0 = by size, the
 // default; 1 = grid-stride form; 2 = tile form at every size), so small test
 // cases run the kernels the default takes at large sizes.
@@ -2584,7 +2700,12 @@ MSX_EXPORT int msx_set_host_mode(int mode)
 MSX_EXPORT int msx_schedule_tree(int which, int p, int n, int* src32, int* P, unsigned* pairmask,
                                  int* chain)
 {
-    if (p < 1 || p > 16 || !src32 || !P || !pairmask || !chain) return MPI_ERR_ARG;
+    if (p < 1 || !src32 || !P || !pairmask || !chain) return MPI_ERR_ARG;
+    // the tree kernels take 16 leaves: the fold trees (16 leaves, each a rank
+    // or a folded pair) reach p = 31, the binomial tree (a leaf per rank) and
+    // the chain (a source per rank) p = 16
+    const bool fold = which == 0 || which == 1 || which == 3;
+    if (p > (fold ? 31 : 16) || n < 0 || n >= p) return MPI_ERR_ARG;
     RankTree t;
     if (which == 0) t = tree_allreduce(p, n);
     else if (which == 1) t = tree_reduce_scatter(p, n);

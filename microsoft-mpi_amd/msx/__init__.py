@@ -182,6 +182,10 @@ def lib():
         "msx_reduce_tree_dev": (i, [ctypes.POINTER(p), i, p, i64, i, i, p]),
         "msx_tune_pack": (i, [i]),
         "msx_copy_dev": (i, [p, p, i64, p]),
+        # tests of the engine's tree / push / copy kernels; arrays as void*
+        "msx_reduce_tree_done_dev": (i, [p, i, ctypes.c_uint, i, i, p, p, i, p, i, p, i, ctypes.c_uint64, i64, i, i, p]),
+        "msx_push_dev": (i, [p, p, p, i, p, i, ctypes.c_uint64, p, p, p, p]),
+        "msx_copy_segs_dev": (i, [p, p, p, i, p]),
         "msx_set_staging_chunk": (i, [i64]),
         "msx_set_host_mode": (i, [i]),
     }

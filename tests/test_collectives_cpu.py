@@ -3,7 +3,7 @@
 1. The collective engine's schedules (expression trees per rank/block,
    msx_schedule_*) evaluated with the oracle's combine reproduce, bit for bit,
    the oracle's step-by-step simulation of the reference schedules
-   (reduce.cpp:3768-4104, 917-1334) for p = 1..9, including the
+   (reduce.cpp:3768-4104, 917-1334) for p = 1..31, including the
    non-power-of-two fold and order-sensitive data (fp32 SUM over a wide
    dynamic range, MAX with NaN and +-0).
 2. world_size-2 gloo: two processes exchange their contributions with
@@ -179,6 +179,51 @@ def test_engine_reduce_schedule_matches_reference_simulation(p, count, opname):
         assert oracle.reduce(op, C.MPI_FLOAT, root, xs, exp) == 0
         got = engine_reduce_result(xs, op, C.MPI_FLOAT, root)
         assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), (p, count, root)
+
+
+# Beyond nine ranks: the patterns tests/test_gpu_engine_kernels.py feeds the
+# tree kernels.  The kernels' 16 leaves admit p <= 31 for the fold trees
+# (allreduce, reduce_scatter halving, reduce Rabenseifner) and p <= 16 for the
+# binomial tree and the pairwise chain (msx_schedule_tree rejects more); the
+# simulator has no rank cap of its own.  Order-sensitive data (_data): fp32
+# SUM over mixed magnitudes, MAX over floats with NaN and +-0.
+@pytest.mark.parametrize("p", range(10, 32))
+@pytest.mark.parametrize("opname", ["MPI_SUM", "MPI_MAX"])
+def test_engine_schedules_match_reference_simulation_up_to_31_ranks(p, opname):
+    op = getattr(C, opname)
+    pof2 = 1 << (p.bit_length() - 1)
+    some = sorted({0, 1, 2 * (p - pof2) % p, p // 2, p - 1})        # folded, unfolded and end ranks
+    # allreduce: recursive doubling (every rank's own lineage) and Rabenseifner (every block)
+    for count in (13, 70001):
+        xs = _data(p, count, op, 100 * p + count % 97)
+        rb = [np.zeros(count, np.float32) for _ in range(p)]
+        assert oracle.allreduce(op, C.MPI_FLOAT, xs, rb) == 0
+        for r in (range(p) if count == 13 else some):
+            got = engine_allreduce_result(xs, op, C.MPI_FLOAT, r)
+            assert np.array_equal(got.view(np.uint32), rb[r].view(np.uint32)), ("allreduce", p, count, r)
+    # reduce: Rabenseifner (> 64 KiB) to p = 31, the binomial tree to p = 16
+    for count in (30000, 13):
+        if count == 13 and p > 16:
+            continue
+        xs = _data(p, count, op, 31 * p + count % 89)
+        assert algo(2, p, count, 4) == (1 if count == 30000 else 4)
+        for root in sorted({0, p - 1, p // 2}):
+            exp = np.zeros(count, np.float32)
+            assert oracle.reduce(op, C.MPI_FLOAT, root, xs, exp) == 0
+            got = engine_reduce_result(xs, op, C.MPI_FLOAT, root)
+            assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), ("reduce", p, count, root)
+    # reduce_scatter: recursive halving to p = 31, the pairwise chain to p = 16
+    for per in (5, 14000):
+        if per == 14000 and p > 16:
+            continue
+        counts = [per + (i % 3) for i in range(p)]
+        assert algo(1, p, sum(counts), 4) == (2 if per == 5 else 3)
+        xs = _data(p, sum(counts), op, 7 * p + per)
+        rb = [np.zeros(c, np.float32) for c in counts]
+        assert oracle.reduce_scatter(op, C.MPI_FLOAT, counts, xs, rb) == 0
+        for r in range(p):
+            got = engine_reduce_scatter_result(xs, counts, op, C.MPI_FLOAT, r)
+            assert np.array_equal(got.view(np.uint32), rb[r].view(np.uint32)), ("reduce_scatter", p, per, r)
 
 
 def test_algorithm_gates_follow_reference_32bit_arithmetic():

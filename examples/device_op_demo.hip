@@ -1,5 +1,6 @@
 // device_op_demo.hip — a device-resident user-defined reduction op: abs-max
-// written with the kernel kit and used in MPI_Allreduce on device buffers.
+// written with the kernel kit, registered with its fused tree form and used in
+// MPI_Allreduce on device buffers.
 //
 //   hipcc --offload-arch=gfx950 -Iinclude examples/device_op_demo.hip \
 //         -Lmicrosoft-mpi_amd/lib -lmsmpi_mi355x -o device_op_demo
@@ -13,8 +14,10 @@
 struct AbsMax {
     __device__ float operator()(const float& in, const float& inout) const { return fmaxf(fabsf(in), fabsf(inout)); }
 };
-// extern "C" int absmax_f32(in, inout, count, datatype, stream, state): enqueues the kit's kernel
-MSX_DEVICE_OP(absmax_f32, float, AbsMax)
+// extern "C" int absmax_f32(in, inout, count, datatype, stream, state): enqueues the kit's pairwise
+// kernel; absmax_f32_tree(srcs, P, pairmask, nleaves, chain, in_left, out, ...): its fused tree, one
+// launch for a collective's whole evaluation
+MSX_DEVICE_OP_TREE(absmax_f32, float, AbsMax)
 
 int main(int argc, char** argv)
 {
@@ -31,7 +34,7 @@ int main(int argc, char** argv)
     if (hipMemcpy(x, h.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return 1;
 
     MPI_Op op;
-    msx_op_create_device(absmax_f32, /*commute=*/1, /*state=*/NULL, &op);
+    msx_op_create_device_tree(absmax_f32, absmax_f32_tree, /*commute=*/1, /*state=*/NULL, &op);
     MPI_Allreduce(x, y, n, MPI_FLOAT, op, MPI_COMM_WORLD);      // the data never leaves the GPU
     MPI_Op_free(&op);
 

@@ -151,6 +151,60 @@ int msx_op_create_device(MSX_Device_function* fn, int commute, void* state, MPI_
 /* 1 device op, 0 any other valid op, -1 invalid */
 int msx_op_is_device(MPI_Op op);
 
+/* The fused tree form of a device user op: ONE call evaluates the whole
+ * reduction tree of a collective instead of p - 1 calls of the pairwise
+ * function, so each contribution is read once and the result written once.
+ *
+ * A device tree function enqueues one evaluation on `stream` under the rules
+ * of MSX_Device_function (no synchronisation, no MPI calls, possibly on a
+ * library thread).  The slot layout is msx_reduce_tree_spec_dev's: P leaves (a
+ * power of two <= 16) in 2P slots, leaf k in srcs[2k] and, when bit k of
+ * pairmask is set, its fold pair in srcs[2k+1]; leaves >= nleaves are absent
+ * (nleaves == 0: all present); with chain != 0, P sources (2..16) in srcs[0..P),
+ * pairmask == 0 and nleaves == 0.  srcs is a HOST array of device pointers
+ * (typed bases for a derived datatype); slots of absent leaves and of unpaired
+ * leaves are not to be read.  Sources are not written; `out` is one of the
+ * sources or disjoint from all of them.
+ *
+ * The value is defined by the pairwise function g(in, inout) = fn's result:
+ *   in_left == 0  leaf k = g(in = s[2k+1], inout = s[2k]) when paired, else
+ *                 s[2k]; a node = g(in = right, inout = left); a node whose
+ *                 right subtree is absent passes its left value up; a chain is
+ *                 v = s[0], then v = g(in = s[k], inout = v), k = 1..P-1.
+ *   in_left == 1  every role swapped: a pair = g(in = s[2k], inout = s[2k+1]),
+ *                 a node = g(in = left, inout = right), a chain step
+ *                 v = g(in = v, inout = s[k]).
+ * Returns MPI_SUCCESS (enqueued), MSX_TREE_DECLINED (nothing enqueued: the
+ * library runs the pairwise evaluation for that call) or an MPI error class,
+ * which fails the calling MPI call.
+ *
+ * msx_op_create_device_tree registers fn (required) with tree_fn (NULL: the op
+ * is exactly msx_op_create_device's).  MPI_Allreduce, MPI_Reduce and
+ * MPI_Reduce_scatter[_block] and their non-blocking forms call tree_fn once
+ * per evaluating rank when the shape fits 16 leaves (p <= 31 for the fold
+ * trees, p <= 16 for binomial trees and chains); MPI_Scan / MPI_Exscan,
+ * MPI_Reduce_local and larger shapes call fn as before.
+ * include/msx_device_op.h: msx_kit::tree and MSX_DEVICE_OP_TREE write one. */
+#define MSX_TREE_DECLINED (-1)
+typedef int (MSX_Device_tree_function)(const void* const* srcs, int P, unsigned pairmask, int nleaves,
+                                       int chain, int in_left, void* out, int64_t count,
+                                       MPI_Datatype datatype, void* stream, void* state);
+int msx_op_create_device_tree(MSX_Device_function* fn, MSX_Device_tree_function* tree_fn,
+                              int commute, void* state, MPI_Op* op);
+/* 1 device op with a tree function, 0 any other valid op, -1 invalid */
+int msx_op_has_device_tree(MPI_Op op);
+/* The op's tree function on the caller's memory and stream (tests and probes);
+ * never the pairwise path.  Bad arguments are MPI_ERR_ARG before any GPU is
+ * touched: null srcs or out, a tree P that is no power of two in 1..16, a
+ * chain P outside 2..16, nleaves outside 0..P, pairmask bits at or above the
+ * leaves present, a chain with a pairmask or nleaves, in_left not 0 or 1.  A
+ * negative count is MPI_ERR_COUNT, an op without a tree function MPI_ERR_OP;
+ * without a GPU MPI_ERR_OTHER and the function is never entered; count == 0
+ * succeeds without a call; a decline is returned as MSX_TREE_DECLINED. */
+int msx_reduce_tree_user_dev(const void* const* srcs, int P, unsigned pairmask, int nleaves, int chain,
+                             int in_left, void* out, int64_t count, MPI_Datatype datatype, MPI_Op op,
+                             void* stream);
+
 /* packed[i*size + b] <- typed[i*extent + map(b)] for `count` instances of a
  * committed datatype (predefined or derived); typed is the buffer address the
  * type map is relative to.  Device pointers, stream-ordered. */
@@ -238,6 +292,15 @@ int msx_set_host_mode(int mode);
  * p is MPI_ERR_ARG. */
 int msx_schedule_tree(int which, int p, int n, int* src32, int* P, unsigned* pairmask,
                       int* chain);
+/* the spec a device-op collective hands to the op's tree function (a pure
+ * function): which = 0 MPI_Allreduce for real rank n, 1 MPI_Reduce for root n,
+ * 2 MPI_Reduce_scatter for real rank n (commutative: the recursive-halving tree
+ * or the pairwise chain by the gate on total_count * type_size; non-commutative:
+ * the allreduce of the whole vector).  src32[i] = real rank in slot i (-1 =
+ * empty).  MPI_ERR_ARG when the shape does not fit 16 leaves (the collective
+ * then keeps the pairwise evaluation) or p < 2. */
+int msx_schedule_devop_tree(int which, int p, int n, int commutative, int64_t total_count, int type_size,
+                            int* src32, int* P, unsigned* pairmask, int* nleaves, int* chain, int* in_left);
 /* which = 0 allreduce, 1 reduce_scatter, 2 reduce: 0 recursive doubling,
  * 1 Rabenseifner, 2 recursive halving, 3 pairwise, 4 binomial */
 int msx_schedule_algo(int which, int p, int64_t count, int type_size);

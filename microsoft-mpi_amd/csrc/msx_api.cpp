@@ -48,6 +48,7 @@ struct UserOp {
     bool live = false;
     MSX_Device_function* dev_fn = nullptr;   // msx_op_create_device: fn is null
     void* dev_state = nullptr;
+    MSX_Device_tree_function* dev_tree = nullptr;   // msx_op_create_device_tree
 };
 std::mutex g_op_mu;
 std::vector<UserOp> g_user_ops;
@@ -205,6 +206,7 @@ int v_op_handle(MPI_Op op, OpRef* out)
         out->user_fn = nullptr;
         out->dev_fn = nullptr;
         out->dev_state = nullptr;
+        out->dev_tree = nullptr;
         out->commutative = (idx != O_REPLACE && idx != O_NOOP);
         return MPI_SUCCESS;
     }
@@ -218,6 +220,7 @@ int v_op_handle(MPI_Op op, OpRef* out)
     out->user_fn = g_user_ops[idx].fn;
     out->dev_fn = g_user_ops[idx].dev_fn;
     out->dev_state = g_user_ops[idx].dev_state;
+    out->dev_tree = g_user_ops[idx].dev_tree;
     out->commutative = g_user_ops[idx].commute;
     return MPI_SUCCESS;
 }
@@ -681,25 +684,48 @@ MSX_EXPORT int MPI_Op_create(MPI_User_function* user_fn, int commute, MPI_Op* op
     size_t idx = 0;
     while (idx < g_user_ops.size() && g_user_ops[idx].live) ++idx;
     if (idx == g_user_ops.size()) g_user_ops.push_back(UserOp{});
-    g_user_ops[idx] = UserOp{user_fn, commute != 0, true, nullptr, nullptr};
+    g_user_ops[idx] = UserOp{user_fn, commute != 0, true, nullptr, nullptr, nullptr};
     *op = kUserOpBase | (int)idx;
     return MPI_SUCCESS;
 }
 
 // A user op whose function enqueues its combine on a HIP stream (msx.h): the
 // same MPID_Op pool and handle layout as MPI_Op_create.
-MSX_EXPORT int msx_op_create_device(MSX_Device_function* fn, int commute, void* state, MPI_Op* op)
+namespace {
+int device_op_create(MSX_Device_function* fn, MSX_Device_tree_function* tree_fn, int commute, void* state, MPI_Op* op)
 {
-    MSX_REQUIRE_INIT("msx_op_create_device");
     if (fn == nullptr) { set_error("null device function"); return MPI_ERR_ARG; }
     if (op == nullptr) { set_error("null op"); return MPI_ERR_ARG; }
     std::lock_guard<std::mutex> g(g_op_mu);
     size_t idx = 0;
     while (idx < g_user_ops.size() && g_user_ops[idx].live) ++idx;
     if (idx == g_user_ops.size()) g_user_ops.push_back(UserOp{});
-    g_user_ops[idx] = UserOp{nullptr, commute != 0, true, fn, state};
+    g_user_ops[idx] = UserOp{nullptr, commute != 0, true, fn, state, tree_fn};
     *op = kUserOpBase | (int)idx;
     return MPI_SUCCESS;
+}
+}  // namespace
+
+MSX_EXPORT int msx_op_create_device(MSX_Device_function* fn, int commute, void* state, MPI_Op* op)
+{
+    MSX_REQUIRE_INIT("msx_op_create_device");
+    return device_op_create(fn, nullptr, commute, state, op);
+}
+
+// The same op with a fused tree function beside the pairwise one (msx.h): the
+// reduction collectives call it once per evaluating rank (msx_devop.cpp).
+MSX_EXPORT int msx_op_create_device_tree(MSX_Device_function* fn, MSX_Device_tree_function* tree_fn, int commute,
+                                         void* state, MPI_Op* op)
+{
+    MSX_REQUIRE_INIT("msx_op_create_device_tree");
+    return device_op_create(fn, tree_fn, commute, state, op);
+}
+
+MSX_EXPORT int msx_op_has_device_tree(MPI_Op op)
+{
+    OpRef r;
+    if (v_op_handle(op, &r) != MPI_SUCCESS) return -1;
+    return r.dev_tree ? 1 : 0;
 }
 
 MSX_EXPORT int msx_op_is_device(MPI_Op op)
@@ -2536,6 +2562,34 @@ MSX_EXPORT int msx_reduce_tree_spec_dev(const void* const* srcs, int P, unsigned
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "tree kernel launch");
 }
 
+// A device user op's tree function (msx_op_create_device_tree) on the caller's
+// memory and stream: the call a collective makes, without the collective.
+// Never the pairwise path: an op without a tree function is MPI_ERR_OP and a
+// decline comes back as MSX_TREE_DECLINED.
+MSX_EXPORT int msx_reduce_tree_user_dev(const void* const* srcs, int P, unsigned pairmask, int nleaves, int chain,
+                                        int in_left, void* out, int64_t count, MPI_Datatype dt, MPI_Op op,
+                                        void* stream)
+{
+    OpRef r;
+    int rc = v_op_handle(op, &r);
+    if (rc != MPI_SUCCESS) return rc;
+    if (!r.dev_tree) { set_error("MPI_Op 0x%x has no device tree function", op); return MPI_ERR_OP; }
+    const bool pow2 = P >= 1 && P <= 16 && (P & (P - 1)) == 0;
+    const bool shape = chain ? (P >= 2 && P <= 16 && pairmask == 0 && nleaves == 0)
+                             : (pow2 && nleaves >= 0 && nleaves <= P && (pairmask >> (nleaves ? nleaves : P)) == 0);
+    if (!srcs || !out || !shape || (in_left != 0 && in_left != 1)) {
+        set_error("bad tree spec (P=%d pairmask=0x%x nleaves=%d chain=%d in_left=%d)", P, pairmask, nleaves, chain,
+                  in_left);
+        return MPI_ERR_ARG;
+    }
+    if (count < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
+    if (count == 0) return MPI_SUCCESS;
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;      // no GPU: MPI_ERR_OTHER, the function is never entered
+    return device_op_tree_call(r, dt, srcs, P, pairmask, nleaves, chain != 0, in_left, out, (size_t)count,
+                               static_cast<hipStream_t>(stream));
+}
+
 // The engine's local copy (the collect step of the collectives, MPIR_Localcopy
 // of device data, mpid/pt2pt.cpp:929-948): k_copy_segs' XCD-contiguous 4-KiB
 // tiles up to 16 MiB, k_copy_dram's one-wave dispatch-order grid above.
@@ -2720,6 +2774,28 @@ MSX_EXPORT int msx_schedule_tree(int which, int p, int n, int* src32, int* P, un
     }
     *pairmask = t.pairmask;
     *chain = t.chain ? 1 : 0;
+    return MPI_SUCCESS;
+}
+
+// The spec a device-op collective hands to the op's tree function
+// (devop_tree_spec, msx_schedule.cpp): which 0 allreduce for real rank n,
+// 1 reduce for root n, 2 reduce_scatter for real rank n.
+MSX_EXPORT int msx_schedule_devop_tree(int which, int p, int n, int commutative, int64_t total_count, int type_size,
+                                       int* src32, int* P, unsigned* pairmask, int* nleaves, int* chain, int* in_left)
+{
+    if (!src32 || !P || !pairmask || !nleaves || !chain || !in_left || which < 0 || which > 2 || p < 1 || n < 0 ||
+        n >= p || total_count < 0 || type_size < 0)
+        return MPI_ERR_ARG;
+    RankTree t;
+    int il = 0;
+    if (!devop_tree_spec(which, p, n, commutative != 0, (size_t)total_count, type_size, &t, &il)) return MPI_ERR_ARG;
+    const int used = t.chain ? t.P : 2 * (t.nleaves ? t.nleaves : t.P);
+    for (int i = 0; i < 32; ++i) src32[i] = i < used ? t.src[i] : -1;
+    *P = t.P;
+    *pairmask = t.pairmask;
+    *nleaves = t.nleaves;
+    *chain = t.chain ? 1 : 0;
+    *in_left = il;
     return MPI_SUCCESS;
 }
 

@@ -185,6 +185,17 @@ int device_op_call(const OpRef& op, MPI_Datatype dt, const void* in, void* inout
     return rc;
 }
 
+// MSX_Device_tree_function contract (msx.h): enqueue only; a decline is the
+// caller's to handle, any other class is ours.
+int device_op_tree_call(const OpRef& op, MPI_Datatype dt, const void* const* srcs, int P, unsigned pairmask,
+                        int nleaves, int chain, int in_left, void* out, size_t count, hipStream_t s)
+{
+    const int rc = op.dev_tree(srcs, P, pairmask, nleaves, chain, in_left, out, (int64_t)count, dt,
+                               static_cast<void*>(s), op.dev_state);
+    if (rc != MPI_SUCCESS && rc != MSX_TREE_DECLINED) set_error("device tree function returned error class %d", rc);
+    return rc;
+}
+
 namespace {
 
 // HBM staging of host operands for device user ops (grows, never shrinks);

@@ -54,6 +54,9 @@ struct OpRef {
     // null; dev_fn enqueues the combine on a stream and gets `dev_state`
     MSX_Device_function* dev_fn = nullptr;
     void* dev_state = nullptr;
+    // msx_op_create_device_tree: one call evaluates a collective's whole tree
+    // (null: the pairwise calls of dev_fn)
+    MSX_Device_tree_function* dev_tree = nullptr;
 };
 
 // MSMPI_FORCE_ASYNC_WORKFLOW (mpid/env.cpp:1381-1384, read at MPI_Init with
@@ -89,6 +92,11 @@ int local_combine(const OpRef& op, MPI_Datatype dt, const void* in, void* inout,
 // One call of a device user function on `s` with typed bases (enqueue only);
 // the function's error class fails the caller.
 int device_op_call(const OpRef& op, MPI_Datatype dt, const void* in, void* inout, size_t count, hipStream_t s);
+// One call of a device op's tree function (op.dev_tree, MSX_Device_tree_function)
+// on `s`: MPI_SUCCESS, MSX_TREE_DECLINED (nothing enqueued) or the function's
+// error class, which fails the caller.
+int device_op_tree_call(const OpRef& op, MPI_Datatype dt, const void* const* srcs, int P, unsigned pairmask,
+                        int nleaves, int chain, int in_left, void* out, size_t count, hipStream_t s);
 
 // Copy `bytes` between any two buffers (host or device), blocking.
 int copy_any(void* dst, const void* src, size_t bytes);

@@ -19,6 +19,13 @@
 // and commutative reduce_scatter (over the rank's block), at most p - 1 for
 // scan / exscan.  Non-commutative reduce_scatter is an allreduce of the whole
 // vector, as on the host path.
+//
+// An op with a tree function (msx_op_create_device_tree) evaluates the same
+// value in ONE call: devop_tree_spec (msx_schedule.cpp) names the tree the
+// calls above build, the sources are the gathered blocks and the result lands
+// in the block of the rank's own contribution.  Scan / exscan (partials that
+// are not one such tree), shapes beyond 16 leaves and a declined call keep the
+// pairwise calls.
 #include "msx_engine.h"
 
 #include <algorithm>
@@ -90,6 +97,25 @@ struct Eval {
     void call(const char* in, char* io)
     {
         if (rc == MPI_SUCCESS) rc = device_op_call(op, dt, in - m.lo, io - m.lo, count, s);
+    }
+    // The whole evaluation as one call of the op's tree function: collective
+    // `which` of devop_tree_spec for rank (or root) n over the blocks x[r],
+    // the result into `out`.  false: nothing was enqueued (no tree function, a
+    // shape beyond 16 leaves or a decline) and the pairwise calls are due.
+    bool tree(int which, int p, int n, size_t gate_count, const std::vector<char*>& x, char* out)
+    {
+        if (!op.dev_tree || rc != MPI_SUCCESS) return false;
+        RankTree t;
+        int in_left = 0;
+        if (!devop_tree_spec(which, p, n, op.commutative, gate_count, gate_type_size(dt, false), &t, &in_left))
+            return false;
+        const void* srcs[32];
+        for (int i = 0; i < 32; ++i) srcs[i] = t.src[i] >= 0 ? x[(size_t)t.src[i]] - m.lo : nullptr;
+        const int r = device_op_tree_call(op, dt, srcs, t.P, t.pairmask, t.nleaves, t.chain ? 1 : 0, in_left,
+                                          out - m.lo, count, s);
+        if (r == MSX_TREE_DECLINED) return false;
+        rc = r;
+        return true;
     }
 };
 
@@ -238,7 +264,7 @@ int devop_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, M
     const int rg = gather_all(c, w, b, ev.m.bytes, &x, ev.s);
     if (rc == MPI_SUCCESS) rc = rg;
     if (rc != MPI_SUCCESS) return rc;
-    char* res = eval_allreduce(ev, x, p, me, op.commutative);
+    char* res = ev.tree(0, p, me, count, x, x[(size_t)me]) ? x[(size_t)me] : eval_allreduce(ev, x, p, me, op.commutative);
     return finish(ev, res - ev.m.lo, recvbuf, count);
 }
 
@@ -270,7 +296,7 @@ int devop_reduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_
     const int rg = dev_gather(c->tp, w, send, send_n, x, recv_n, ev.m.bytes, ev.s);
     if (rc == MPI_SUCCESS) rc = rg;
     if (rc != MPI_SUCCESS || me != root) return rc;
-    char* res = eval_reduce(ev, x, p, root, op.commutative);
+    char* res = ev.tree(1, p, root, count, x, x[(size_t)me]) ? x[(size_t)me] : eval_reduce(ev, x, p, root, op.commutative);
     return finish(ev, res - ev.m.lo, recvbuf, count);
 }
 
@@ -302,7 +328,7 @@ int devop_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const int*
         const int rg = gather_all(c, w, b, mf.bytes, &x, s);
         if (rc == MPI_SUCCESS) rc = rg;
         if (rc != MPI_SUCCESS) return rc;
-        char* res = eval_allreduce(ev, x, p, me, false);
+        char* res = ev.tree(2, p, me, total, x, x[(size_t)me]) ? x[(size_t)me] : eval_allreduce(ev, x, p, me, false);
         return finish(ev, res - mf.lo + (int64_t)disp[(size_t)me] * unit, recvbuf, mycnt);
     }
 
@@ -345,7 +371,7 @@ int devop_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const int*
     const int n = newrank_of(me, p);
     const RankTree t = (algo == A_RS_PAIRWISE) ? tree_pairwise(p, me)
                                                : tree_reduce_scatter(p, n >= 0 ? n : newrank_of(me + 1, p));
-    char* res = eval_tree_dev(ev, t, x);
+    char* res = ev.tree(2, p, me, total, x, x[(size_t)me]) ? x[(size_t)me] : eval_tree_dev(ev, t, x);
     return finish(ev, res - mb.lo, recvbuf, mycnt);
 }
 

@@ -226,4 +226,68 @@ RankTree tree_pairwise(int p, int r)
     return t;
 }
 
+// The device-op collectives' evaluations (msx_devop.cpp: rd_value,
+// eval_reduce, eval_tree_dev) written as one tree each.  in_left = 0: the
+// engine's roles, left operand `inout`; in_left = 1: left operand `in`.
+//   allreduce, commutative: rd_value calls (in = partner's value, inout = own)
+//     at every step, so rank n's value is tree_allreduce of its newrank (a
+//     folded even rank takes its odd neighbour's); the fold is (in = even rank,
+//     inout = odd rank), the odd rank in slot 2k.
+//   allreduce, non-commutative: rd_value makes the lower newrank's value `in`
+//     at every step, whichever rank asks: the tree over newranks 0..P-1 in
+//     order with the left operand `in`, the fold pair (even, odd) in that order.
+//   reduce: eval_reduce's binomial tree over root-relative ranks (commutative,
+//     in = right) or over ranks from 0 (non-commutative, in = left).
+//   reduce_scatter, commutative: eval_tree_dev's RankTree as it is.
+bool devop_tree_spec(int which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
+                     int* in_left)
+{
+    if (p < 2 || n < 0 || n >= p) return false;
+    const bool as_allreduce = which == 0 || (which == 2 && !commutative);
+    if (as_allreduce) {
+        if (p > 31) return false;
+        if (commutative) {
+            const int rem = p - pof2_floor(p);
+            const int src = (n < 2 * rem && (n & 1) == 0) ? n + 1 : n;
+            *t = tree_allreduce(p, newrank_of(src, p));
+            *in_left = 0;
+            return true;
+        }
+        const int P = pof2_floor(p), rem = p - P;
+        RankTree r;
+        r.P = P;
+        for (int i = 0; i < 32; ++i) r.src[i] = -1;
+        for (int k = 0; k < P; ++k) {
+            const int odd = real_of_newrank(k, p);
+            if (k < rem) {
+                r.src[2 * k] = odd - 1;
+                r.src[2 * k + 1] = odd;
+                r.pairmask |= 1u << k;
+            } else {
+                r.src[2 * k] = odd;
+            }
+        }
+        *t = r;
+        *in_left = 1;
+        return true;
+    }
+    if (which == 1) {
+        if (p > 16) return false;
+        *t = tree_reduce_binomial(p, commutative ? n : 0);
+        *in_left = commutative ? 0 : 1;
+        return true;
+    }
+    if (which != 2) return false;
+    if (reduce_scatter_algo(p, total_count, type_size, true) == A_RS_PAIRWISE) {
+        if (p > 16) return false;
+        *t = tree_pairwise(p, n);
+    } else {
+        if (p > 31) return false;
+        const int nr = newrank_of(n, p);
+        *t = tree_reduce_scatter(p, nr >= 0 ? nr : newrank_of(n + 1, p));
+    }
+    *in_left = 0;
+    return true;
+}
+
 }  // namespace msx

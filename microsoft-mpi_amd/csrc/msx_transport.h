@@ -155,6 +155,13 @@ RankTree tree_reduce_rsag(int p, int n);
 RankTree tree_ireduce_rsag(int p, int n, int root);
 //   reduce, binomial:     leaves x_{(k + root) % p}, k < p, of a nextpow2(p) tree
 RankTree tree_reduce_binomial(int p, int root);
+// The tree a device-op collective (msx_devop.cpp) hands to the op's tree
+// function, and its operand roles (MSX_Device_tree_function's in_left): which
+// 0 allreduce for real rank n, 1 reduce for root n, 2 reduce_scatter for real
+// rank n (total_count x type_size: the commutative gate).  false: p < 2 or the
+// shape exceeds 16 leaves, and the collective keeps its pairwise evaluation.
+bool devop_tree_spec(int which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
+                     int* in_left);
 // Bytes per element the algorithm gates multiply the count by: the blocking
 // calls use MPI_Type_size (reduce.cpp:151, :1705, :3821), the NBC task lists
 // of MPI_Iallreduce / MPI_Ireduce the extent (:4712-4717, :6695-6701; 16 vs

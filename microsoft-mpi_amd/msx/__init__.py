@@ -172,6 +172,12 @@ def lib():
         "msx_operands_on_device": (i, [p, p]),
         "msx_op_create_device": (i, [p, i, p, ctypes.POINTER(i)]),
         "msx_op_is_device": (i, [i]),
+        "msx_op_create_device_tree": (i, [p, p, i, p, ctypes.POINTER(i)]),
+        "msx_op_has_device_tree": (i, [i]),
+        "msx_reduce_tree_user_dev": (i, [ctypes.POINTER(p), i, ctypes.c_uint, i, i, i, p, i64, i, i, p]),
+        "msx_schedule_devop_tree": (i, [i, i, i, i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
+                                        ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(i), ctypes.POINTER(i),
+                                        ctypes.POINTER(i)]),
         "msx_schedule_two_step": (i64, [i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i64), i64]),
         "msx_reduce_local_multi": (i, [p, p, i64, i, i, i]),
         "msx_reduce_tree_spec_dev": (i, [ctypes.POINTER(p), i, ctypes.c_uint, i, i, p, i64, i, i, p]),

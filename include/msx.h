@@ -319,6 +319,11 @@ int msx_schedule_newrank(int rank, int p);
  * chunks; returns the range count, -1 if cap triples do not suffice */
 int64_t msx_schedule_two_step(int p, int64_t count, int esz, int rank, int64_t* chunk_el, int64_t* out,
                               int64_t cap);
+/* the same plan with chunks of chunk_el elements, the caller's choice (the
+ * host-barrier Rabenseifner schedule cuts chunks of p sub-slots);
+ * *chunk_el_out = chunk_el */
+int64_t msx_schedule_pieces(int p, int64_t count, int64_t chunk_el, int rank, int64_t* chunk_el_out, int64_t* out,
+                            int64_t cap);
 int msx_schedule_block(int p, int64_t count, int n, int64_t* start, int64_t* len);
 
 #ifdef __cplusplus

@@ -323,6 +323,11 @@ size_t sub_len(size_t C, int p)
     return (per - sub_skew(per)) & ~(size_t)255;
 }
 
+// Half an IN sub-slot for p ranks, whole 256-byte lines: what one GPU-flag
+// call, chunk or round may write into a peer's sub-slot while the other half
+// is still being read.
+size_t half_bytes(int p) { return (sub_len(chunk_bytes(), p) / 2) & ~(size_t)255; }
+
 namespace {
 // IN area of a window: p sub-slots sub_skew apart, C bytes in all
 size_t in_bytes(size_t C, int /*p*/) { return C; }

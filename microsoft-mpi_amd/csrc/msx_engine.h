@@ -192,6 +192,7 @@ size_t chunk_bytes();
 size_t rma_bytes_for(int share);   // passive-target staging size for `share` ranks per GPU
 size_t sub_skew(size_t per_rank);
 size_t sub_len(size_t C, int p);
+size_t half_bytes(int p);          // one half of an IN sub-slot (the GPU-flag schedules' unit)
 
 // Every rank's engine window as this process maps it (layout: msx_engine.cpp,
 // "window collectives")

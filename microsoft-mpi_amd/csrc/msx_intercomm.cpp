@@ -156,7 +156,7 @@ constexpr size_t kP2PData = 1024, kP2PAck = 1536;
 
 int p2p_chunks(Comm* u, size_t bytes, size_t* chunk)
 {
-    const size_t Qh = (sub_len(chunk_bytes(), u->size) / 2) & ~(size_t)255;
+    const size_t Qh = half_bytes(u->size);
     *chunk = Qh;
     return (int)((bytes + Qh - 1) / Qh);
 }

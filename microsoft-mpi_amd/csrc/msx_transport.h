@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <functional>
 #include <future>
 #include <vector>
@@ -128,11 +129,18 @@ int reduce_scatter_algo(int p, size_t total_count, int type_size, bool commutati
 int reduce_algo(int p, size_t count, int type_size, bool builtin);
 // allreduce Rabenseifner blocks: block j = [start, start+len), computed at newrank owner
 void allreduce_block(int p, size_t count, int j, size_t* start, size_t* len);
-// the pipelined two-step allreduce's chunk plan (msx_collectives.cpp)
+// the Rabenseifner schedules' piece plan for one chunk (msx_collectives.cpp):
+// the chunk's len elements in p pieces of pel, piece r = [lo(r), hi(r)); one
+// rank's piece [plo, phi) in ranges cut where the owner newrank changes
 struct TwoStepRange { size_t e0, e1; int owner; };
+struct Pieces {
+    size_t len = 0, pel = 0, plo = 0, phi = 0;
+    std::vector<TwoStepRange> ranges;
+    size_t lo(int r) const { return std::min(len, (size_t)r * pel); }
+    size_t hi(int r) const { return std::min(len, (size_t)(r + 1) * pel); }
+};
 size_t two_step_chunk_el(int p, size_t esz);
-void two_step_plan(int p, size_t count, size_t pc_el, size_t ci, int me, std::vector<TwoStepRange>* ranges,
-                   size_t* plo, size_t* phi, size_t* len);
+void piece_plan(int p, size_t count, size_t o, size_t len, int me, Pieces* pc);
 int allreduce_block_owner(int p, int j);           // newrank that owns block j
 int allreduce_block_of_newrank(int p, int n);
 // Tree spec (in real ranks) for the value newrank n computes:

@@ -834,7 +834,7 @@ def test_intercommunicators_six_processes():
 @pytest.mark.parametrize("p", [2, 3, 5, 6, 7, 8, 9, 16, 32])
 def test_two_step_chunk_plan_covers_and_keeps_owners(p):
     """The pipelined two-step allreduce's chunk plan (msx_schedule_two_step,
-    the function do_allreduce itself runs): over all ranks and chunks the
+    piece_plan with allreduce_two_step's chunk length): over all ranks and chunks the
     ranges cover [0, count) exactly once, and each lies inside the block of
     the owner it is evaluated with (reduce.cpp:3927-4066's block of newrank
     `owner`) -- so cutting a message into chunks changes the work split, never
@@ -864,3 +864,81 @@ def test_two_step_chunk_plan_covers_and_keeps_owners(p):
             cover.sort()
             assert cover[0][0] == 0 and cover[-1][1] == count
             assert all(a[1] == b[0] for a, b in zip(cover, cover[1:])), (p, count)
+
+
+def _pieces(p, count, chunk_el, rank):
+    """msx_schedule_pieces for one rank as an (n, 3) int64 array"""
+    L = msx.lib()
+    i64 = ctypes.c_int64
+    cap = (count + chunk_el - 1) // chunk_el + 64
+    out, ce = np.zeros(3 * cap, np.int64), i64()
+    n = L.msx_schedule_pieces(p, count, chunk_el, rank, ctypes.byref(ce),
+                              out.ctypes.data_as(ctypes.POINTER(i64)), cap)
+    assert n >= 0 and ce.value == chunk_el, (p, count, chunk_el, rank, n)
+    return out[:3 * n].reshape(n, 3)
+
+
+def _pieces_restated(p, count, ce):
+    """The host-barrier Rabenseifner loop of allreduce as it stood inline before
+    the schedules shared one plan, restated over whole arrays: chunk [o, o + len)
+    in p pieces of qv = ceil(len / p) rounded up to 16 elements, piece r =
+    [lo_of(r), hi_of(r)), each cut where allreduce_block's block j (start
+    j * (count // pof2), the last one to count) ends, owner
+    allreduce_block_owner(p, j) = bitrev(j).  Returns per rank the (global e0,
+    global e1, owner) triples in the loop's order."""
+    pof2 = 1 << (p.bit_length() - 1)
+    bits = pof2.bit_length() - 1
+    bitrev = np.array([int(format(j, "0%db" % bits)[::-1], 2) if bits else 0 for j in range(pof2)], np.int64)
+    rs = count // pof2
+    o = np.arange(0, count, ce, dtype=np.int64)[:, None]
+    ln = np.minimum(ce, count - o)
+    qv = ((ln + p - 1) // p + 15) & ~15
+    r = np.arange(p, dtype=np.int64)[None, :]
+    lo, hi = o + np.minimum(ln, r * qv), o + np.minimum(ln, (r + 1) * qv)      # lo_of, hi_of, global
+    keep = hi > lo
+    lo, hi, rank = lo[keep], hi[keep], np.broadcast_to(r, keep.shape)[keep]  # chunk-major, rank-minor: ascending
+    starts = np.arange(1, pof2, dtype=np.int64) * rs if rs else np.zeros(0, np.int64)
+    e0 = np.unique(np.concatenate([lo, starts]))
+    e1 = np.concatenate([e0[1:], [count]])
+    who = rank[np.searchsorted(lo, e0, side="right") - 1]
+    j = np.minimum(pof2 - 1, e0 // rs) if rs else np.full(e0.shape, pof2 - 1)
+    tri = np.stack([e0, e1, bitrev[j]], axis=1)
+    return [tri[who == k] for k in range(p)]
+
+
+@pytest.mark.parametrize("p", [2, 3, 4, 5, 6, 7, 8, 9, 16, 31])
+def test_piece_plan_any_chunk_length(p):
+    """msx_schedule_pieces: the one piece plan (piece_plan) behind both
+    Rabenseifner schedules, allreduce_two_step and allreduce_rsag_barrier, for
+    chunk lengths as the host-barrier schedule cuts them (p sub-slots of whole
+    16-element granules) and one longer than the message.  (a) over all ranks
+    and chunks the ranges tile [0, count) exactly once; (b) every range lies in
+    one block of msx_schedule_block, that of its owner; (c) the triples are
+    those of the former inline host-barrier loop, restated in numpy above;
+    (d) with the two-step chunk length they are msx_schedule_two_step's."""
+    L = msx.lib()
+    i64 = ctypes.c_int64
+    pof2 = 1 << (p.bit_length() - 1)
+    for count in (1, p - 1, 1000, 300001):
+        blocks = np.array([schedule_block(p, count, n) for n in range(pof2)], np.int64)
+        for chunk_el in (16 * p, 4096 * p, count + 16 * p):
+            got = [_pieces(p, count, chunk_el, r) for r in range(p)]
+            want = _pieces_restated(p, count, chunk_el)
+            for r in range(p):                                                      # (c)
+                assert np.array_equal(got[r], want[r]), (p, count, chunk_el, r)
+            a = np.concatenate(got)
+            a = a[np.argsort(a[:, 0], kind="stable")]
+            assert a[0, 0] == 0 and a[-1, 1] == count and (a[:, 0] < a[:, 1]).all()  # (a)
+            assert np.array_equal(a[:-1, 1], a[1:, 0]), (p, count, chunk_el)
+            st, ln = blocks[a[:, 2], 0], blocks[a[:, 2], 1]                          # (b)
+            assert (st <= a[:, 0]).all() and (a[:, 1] <= st + ln).all(), (p, count, chunk_el)
+        for esz in (4, 8):                                                           # (d)
+            ce = i64()
+            L.msx_schedule_two_step(p, count, esz, 0, ctypes.byref(ce), (i64 * 3)(), 1)
+            assert ce.value > 0
+            for r in range(p):
+                cap = (count + ce.value - 1) // ce.value + 64
+                out = np.zeros(3 * cap, np.int64)
+                n = L.msx_schedule_two_step(p, count, esz, r, ctypes.byref(ce), out.ctypes.data_as(ctypes.POINTER(i64)),
+                                            cap)
+                assert np.array_equal(_pieces(p, count, ce.value, r), out[:3 * n].reshape(n, 3)), (p, count, esz, r)

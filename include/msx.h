@@ -301,6 +301,17 @@ int msx_schedule_tree(int which, int p, int n, int* src32, int* P, unsigned* pai
  * then keeps the pairwise evaluation) or p < 2. */
 int msx_schedule_devop_tree(int which, int p, int n, int commutative, int64_t total_count, int type_size,
                             int* src32, int* P, unsigned* pairmask, int* nleaves, int* chain, int* in_left);
+/* the pairwise calls that compute one rank's value of a collective with a
+ * user-defined op, host function or device op (a pure function, any p >= 1):
+ * which as above, and 3 MPI_Scan (exclusive = 1: MPI_Exscan) for real rank n.
+ * Block r is rank r's contribution; step k is block steps[2k + 1] =
+ * steps[2k] (op) it, the first `in`, the second `inout`; every block is an
+ * operand exactly once, so the steps run in place.  *result: the block that
+ * holds the value, -1 for rank 0 of an exscan.  p - 1 steps, at most p - 1 for
+ * a scan.  MPI_ERR_ARG, with *nsteps set, when the plan has more than cap
+ * steps (steps holds 2 * cap ints). */
+int msx_schedule_userop_plan(int which, int p, int n, int commutative, int exclusive, int64_t total_count,
+                             int type_size, int* steps, int cap, int* nsteps, int* result);
 /* which = 0 allreduce, 1 reduce_scatter, 2 reduce: 0 recursive doubling,
  * 1 Rabenseifner, 2 recursive halving, 3 pairwise, 4 binomial */
 int msx_schedule_algo(int which, int p, int64_t count, int type_size);

@@ -2788,7 +2788,8 @@ MSX_EXPORT int msx_schedule_devop_tree(int which, int p, int n, int commutative,
         return MPI_ERR_ARG;
     RankTree t;
     int il = 0;
-    if (!devop_tree_spec(which, p, n, commutative != 0, (size_t)total_count, type_size, &t, &il)) return MPI_ERR_ARG;
+    if (!devop_tree_spec((UserColl)which, p, n, commutative != 0, (size_t)total_count, type_size, &t, &il))
+        return MPI_ERR_ARG;
     const int used = t.chain ? t.P : 2 * (t.nleaves ? t.nleaves : t.P);
     for (int i = 0; i < 32; ++i) src32[i] = i < used ? t.src[i] : -1;
     *P = t.P;
@@ -2796,6 +2797,28 @@ MSX_EXPORT int msx_schedule_devop_tree(int which, int p, int n, int commutative,
     *nleaves = t.nleaves;
     *chain = t.chain ? 1 : 0;
     *in_left = il;
+    return MPI_SUCCESS;
+}
+
+// The combine plan both user-op paths execute (userop_plan, msx_schedule.cpp):
+// which 0 allreduce, 2 reduce_scatter, 3 scan (exclusive: exscan) for real
+// rank n, 1 reduce for root n.  steps[2k], steps[2k + 1] = in, io of step k.
+// MPI_ERR_ARG with *nsteps set when the plan has more than cap steps.
+MSX_EXPORT int msx_schedule_userop_plan(int which, int p, int n, int commutative, int exclusive, int64_t total_count,
+                                        int type_size, int* steps, int cap, int* nsteps, int* result)
+{
+    if (!steps || !nsteps || !result || cap < 0 || which < 0 || which > 3 || p < 1 || n < 0 || n >= p ||
+        total_count < 0 || type_size < 0)
+        return MPI_ERR_ARG;
+    const CombinePlan plan =
+        userop_plan((UserColl)which, p, n, commutative != 0, exclusive != 0, (size_t)total_count, type_size);
+    *nsteps = (int)plan.steps.size();
+    *result = plan.result;
+    if (*nsteps > cap) return MPI_ERR_ARG;
+    for (int k = 0; k < *nsteps; ++k) {
+        steps[2 * k] = plan.steps[(size_t)k].in;
+        steps[2 * k + 1] = plan.steps[(size_t)k].io;
+    }
     return MPI_SUCCESS;
 }
 

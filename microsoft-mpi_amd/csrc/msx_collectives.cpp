@@ -17,14 +17,6 @@ size_t out_half_bytes(int p) { return ((chunk_bytes() - half_bytes(p)) / 2) & ~(
 size_t granules(size_t bytes, size_t esz) { return (bytes / esz) & ~(size_t)15; }
 int hip_rc(hipError_t e, const char* what) { return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, what); }
 
-// the newrank whose tree rank `me` evaluates: its own, or for a folded rank
-// its odd neighbour's
-int lineage_of(int me, int p)
-{
-    const int n = newrank_of(me, p);
-    return n >= 0 ? n : newrank_of(me + 1, p);
-}
-
 RankTree rs_tree(int algo, int p, int me)
 {
     return (algo == A_RS_PAIRWISE) ? tree_pairwise(p, me) : tree_reduce_scatter(p, lineage_of(me, p));
@@ -81,127 +73,51 @@ struct RsBlocks {
     size_t cnt(int r) const { return (size_t)recvcounts[r]; }
 };
 
-int host_user_reduce_scatter(Comm* c, const char* src, void* recvbuf, const RsBlocks& b, size_t esz,
-                             MPI_Datatype dt, const OpRef& op)
+// The host user-op entry points: each names its plan (userop_plan,
+// msx_schedule.cpp) and the elements it combines and stores; host_user_run
+// (msx_engine.cpp) gathers and executes.
+//
+// MPI_Reduce_scatter.  Commutative: the builtin schedules (recursive halving or
+// pairwise, same 32-bit gate, reduce.cpp:917-1334) over the rank's own block
+// of every contribution.  Non-commutative: recursive doubling over the whole
+// vector (MPIR_Reduce_scatter_non_commutative, reduce.cpp:1340-1630) -- for a
+// power-of-two p each block is exactly the recursive-doubling allreduce value;
+// other p share its lower-first order -- then block `me` of the result.
+int host_user_reduce_scatter(Comm* c, const char* src, void* recvbuf, const RsBlocks& b, MPI_Datatype dt,
+                             const OpRef& op)
 {
-    const int p = c->size, me = c->rank;
-    // images of the whole input (total elements) and of my block (mycnt);
-    // block r starts disp[r] elements (x extent for a derived type) into it
-    const Img mf = img_of(dt, b.total), mb = img_of(dt, b.mycnt);
-    const int64_t unit = mf.t ? mf.t->extent : (int64_t)esz;
-    std::vector<char> full(mf.bytes);
-    int rc = img_load(mf, src, full.data());
-    if (rc != MPI_SUCCESS) return rc;
-    if (op.commutative) {
-        // commutative user op: the builtin schedules (recursive halving or
-        // pairwise, same 32-bit gate) evaluated on host with the user's
-        // function, reduce.cpp:917-1334
-        std::vector<char> all((size_t)p * mf.bytes);
-        if ((rc = c->tp->allgather(full.data(), mf.bytes, all.data())) != MPI_SUCCESS) return rc;
-        const RankTree t = rs_tree(reduce_scatter_algo(p, b.total, gate_type_size(dt, false), true), p, me);
-        std::vector<const char*> x((size_t)p);
-        for (int r = 0; r < p; ++r)
-            x[(size_t)r] = all.data() + (size_t)r * mf.bytes - mf.lo + (int64_t)b.disp[me] * unit;
-        std::vector<char> res(mb.bytes);
-        eval_tree_host(t, x, res.data() - mb.lo, b.mycnt, dt, op, mb);
-        return b.mycnt ? img_store(mb, b.mycnt, res.data() - mb.lo, recvbuf) : MPI_SUCCESS;
-    }
-    // non-commutative: recursive doubling (MPIR_Reduce_scatter_non_commutative,
-    // reduce.cpp:1340-1630) -- for a power-of-two p each block is exactly the
-    // recursive-doubling allreduce value; other p share its lower-first order
-    std::vector<char> res(mf.bytes);
-    rc = host_user_allreduce(c, full.data() - mf.lo, res.data() - mf.lo, b.total, dt, op);
-    if (rc == MPI_SUCCESS && b.mycnt)
-        rc = img_store(mb, b.mycnt, res.data() - mf.lo + (int64_t)b.disp[me] * unit, recvbuf);
-    return rc;
+    const int me = c->rank;
+    const CombinePlan plan = userop_plan(UserColl::reduce_scatter, c->size, me, op.commutative, false, b.total,
+                                         gate_type_size(dt, false));
+    const size_t first = op.commutative ? b.disp[me] : 0, count = op.commutative ? b.mycnt : b.total;
+    return host_user_run(c, src, recvbuf, b.total, dt, op, b.mycnt ? &plan : nullptr, first, count, b.disp[me],
+                         b.mycnt);
 }
 
 }  // namespace
 
-// MPI_Reduce with a user function (host code): every contribution is gathered
-// to host memory and the reference's binomial tree is evaluated with the
-// user's function (reduce.cpp:440-540): relative ranks from lroot = root for
-// commutative ops, else from 0 with the result sent to root; the parent
-// combines a child's buffer as `in` (commutative) or as `inout` with its own
-// as `in` (non-commutative, "the sender is above us").
+// MPI_Reduce with a user function (host code): the reference's binomial tree
+// (reduce.cpp:440-540) at the root; every other rank only contributes.
 int host_user_reduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
                      const OpRef& op, int root)
 {
-    const int p = c->size, me = c->rank;
-    const Img m = img_of(dt, count);
-    const size_t bytes = m.bytes;
-    std::vector<char> mine(bytes), all((size_t)p * bytes);
-    int rc = img_load(m, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, mine.data());
-    if (rc == MPI_SUCCESS) rc = c->tp->allgather(mine.data(), bytes, all.data());
-    if (rc != MPI_SUCCESS || me != root) return rc;
-    auto call = [&](const char* in, char* io) { img_call(op, dt, m, count, in - m.lo, io - m.lo); };
-    const int lroot = op.commutative ? root : 0;
-    auto buf = [&](int rel) { return all.data() + (size_t)((rel + lroot) % p) * bytes; };
-    std::vector<char> tmp(bytes);
-    for (int mask = 1; mask < p; mask <<= 1) {
-        for (int rel = 0; rel < p; rel += 2 * mask) {     // receivers at this level
-            const int src = rel | mask;
-            if (src >= p) continue;
-            if (op.commutative) {
-                call(buf(src), buf(rel));
-            } else {
-                memcpy(tmp.data(), buf(src), bytes);
-                call(buf(rel), tmp.data());
-                memcpy(buf(rel), tmp.data(), bytes);
-            }
-        }
-    }
-    return img_store(m, count, buf(0) - m.lo, recvbuf);
+    const CombinePlan plan = userop_plan(UserColl::reduce, c->size, root, op.commutative, false, count, 0);
+    return host_user_run(c, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, recvbuf, count, dt, op,
+                         c->rank == root ? &plan : nullptr, 0, count, 0, count);
 }
 
 namespace {
 
-// MPI_Scan / MPI_Exscan: the reference builds a recursive-doubling task list
+// MPI_Scan / MPI_Exscan: the recursive-doubling task list of the reference
 // (IscanBuildTaskList reduce.cpp:5285-5576, IexscanBuildTaskList :5671-5960,
-// NbcTask::ExecuteScan tasks.cpp:694-766).  At step mask, rank r exchanges its
-// partial result with dst = r ^ mask; if r > dst it folds the received value
-// into both its partial and its result (Uop(tmp, partial), Uop(tmp, recvbuf);
-// the first such step of Exscan copies tmp into recvbuf), else only into its
-// partial.  The schedule is run step by step here, the exchange going through
-// the IPC windows, so every combine has the reference's operands and roles.
+// NbcTask::ExecuteScan tasks.cpp:694-766), every combine with the reference's
+// operands and roles.  Rank 0 of an exscan has no value: recvbuf undefined.
 int host_user_scan(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
                    const OpRef& op, bool exclusive)
 {
-    const int p = c->size, me = c->rank;
-    const Img m = img_of(dt, count);
-    const size_t bytes = m.bytes;
-    std::vector<char> mine(bytes), all((size_t)p * bytes);
-    int rc = img_load(m, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, mine.data());
-    if (rc == MPI_SUCCESS) rc = c->tp->allgather(mine.data(), bytes, all.data());
-    if (rc != MPI_SUCCESS) return rc;
-    auto call = [&](const char* in, char* io) { img_call(op, dt, m, count, in - m.lo, io - m.lo); };
-    std::vector<std::vector<char>> part((size_t)p), res((size_t)p);
-    std::vector<bool> have((size_t)p, !exclusive);
-    for (int r = 0; r < p; ++r) {
-        part[r].assign(all.begin() + (size_t)r * bytes, all.begin() + (size_t)(r + 1) * bytes);
-        res[r] = part[r];
-    }
-    for (int mask = 1; mask < p; mask <<= 1) {
-        std::vector<std::vector<char>> snap = part;
-        const bool last = (mask << 1) >= p;
-        for (int r = 0; r < p; ++r) {
-            const int dst = r ^ mask;
-            if (dst >= p || (last && r < dst)) continue;
-            std::vector<char> tmp = snap[dst];
-            if (r > dst) {
-                call(tmp.data(), part[r].data());
-                if (exclusive && !have[r]) { res[r] = tmp; have[r] = true; }
-                else call(tmp.data(), res[r].data());
-            } else if (op.commutative) {
-                call(tmp.data(), part[r].data());
-            } else {
-                call(part[r].data(), tmp.data());
-                part[r] = tmp;
-            }
-        }
-    }
-    if (exclusive && !have[me]) return MPI_SUCCESS;     // rank 0: recvbuf undefined
-    return img_store(m, count, res[me].data() - m.lo, recvbuf);
+    const CombinePlan plan = userop_plan(UserColl::scan, c->size, c->rank, op.commutative, exclusive, count, 0);
+    return host_user_run(c, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, recvbuf, count, dt, op, &plan, 0, count, 0,
+                         count);
 }
 
 // ---- what the window schedules share ---------------------------------------
@@ -765,7 +681,7 @@ int do_reduce_scatter(Comm* comm, const void* sendbuf, void* recvbuf, const int*
     b.mycnt = b.cnt(me);
     b.in_place = (sendbuf == MPI_IN_PLACE);
     const char* src = static_cast<const char*>(b.in_place ? recvbuf : sendbuf);
-    if (op.opidx == O_NULL) return host_user_reduce_scatter(comm, src, recvbuf, b, esz, dt, op);
+    if (op.opidx == O_NULL) return host_user_reduce_scatter(comm, src, recvbuf, b, dt, op);
     int rc = ensure_device();
     if (rc != MPI_SUCCESS) return rc;
     if (rccl_requested())

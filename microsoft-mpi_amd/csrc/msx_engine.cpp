@@ -156,68 +156,38 @@ void img_call(const OpRef& op, MPI_Datatype dt, const Img& m, size_t count, cons
     }
 }
 
-// Evaluate the reference's recursive-doubling order (reduce.cpp:3890-3925,
+// The host executor of a combine plan (userop_plan, msx_schedule.cpp), the
+// whole host user-op path: every rank's image of the `total` elements at `src`
+// is gathered into one flat buffer; the plan's steps then run in place over
+// the p images -- over elements [first, first + count) of each -- and
+// out_count elements from element out_first of the result block go to
+// recvbuf.  plan == nullptr: a rank that only contributes (not the root of a
+// reduce, or no elements of its own).
+int host_user_run(Comm* c, const void* src, void* recvbuf, size_t total, MPI_Datatype dt, const OpRef& op,
+                  const CombinePlan* plan, size_t first, size_t count, size_t out_first, size_t out_count)
+{
+    const Img mf = img_of(dt, total);
+    std::vector<char> mine(mf.bytes), all((size_t)c->size * mf.bytes);
+    int rc = img_load(mf, src, mine.data());
+    if (rc == MPI_SUCCESS) rc = c->tp->allgather(mine.data(), mf.bytes, all.data());
+    if (rc != MPI_SUCCESS || !plan) return rc;
+    const int64_t unit = mf.t ? mf.t->extent : (int64_t)mf.esz;
+    // typed base of element `el` of rank r's contribution
+    auto at = [&](int r, size_t el) { return all.data() + (size_t)r * mf.bytes - mf.lo + (int64_t)el * unit; };
+    const Img mc = img_of(dt, count);
+    for (const CombineStep& s : plan->steps) img_call(op, dt, mc, count, at(s.in, first), at(s.io, first));
+    if (plan->result < 0 || out_count == 0) return MPI_SUCCESS;     // rank 0 of an exscan: recvbuf untouched
+    return img_store(img_of(dt, out_count), out_count, at(plan->result, out_first), recvbuf);
+}
+
+// The reference's recursive-doubling order (reduce.cpp:3890-3925,
 // non-commutative branch included) with the user's function.
 int host_user_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count,
                         MPI_Datatype dt, const OpRef& op)
 {
-    const int p = c->size;
-    const Img m = img_of(dt, count);
-    const size_t bytes = m.bytes;
-    std::vector<char> mine(bytes), all((size_t)p * bytes);
-    int rc = img_load(m, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, mine.data());
-    if (rc == MPI_SUCCESS) rc = c->tp->allgather(mine.data(), bytes, all.data());
-    if (rc != MPI_SUCCESS) return rc;
-    auto call = [&](const char* in, char* io) { img_call(op, dt, m, count, in - m.lo, io - m.lo); };
-    // Simulate every rank's recursive doubling; keep our own rank's result.
-    const int pof2 = pof2_floor(p), rem = p - pof2;
-    std::vector<std::vector<char>> v((size_t)p);
-    for (int r = 0; r < p; ++r) v[r].assign(all.begin() + (size_t)r * bytes, all.begin() + (size_t)(r + 1) * bytes);
-    for (int r = 0; r < 2 * rem; r += 2) call(v[r].data(), v[r + 1].data());   // fold into odd
-    for (int mask = 1; mask < pof2; mask <<= 1) {
-        std::vector<std::vector<char>> nv = v;
-        for (int n = 0; n < pof2; ++n) {
-            const int r = real_of_newrank(n, p), dst = real_of_newrank(n ^ mask, p);
-            if (op.commutative || dst < r) {
-                call(v[dst].data(), nv[r].data());
-            } else {
-                std::vector<char> tmp = v[dst];
-                call(v[r].data(), tmp.data());
-                nv[r] = tmp;
-            }
-        }
-        v.swap(nv);
-    }
-    const int me = c->rank;
-    const int src = (me < 2 * rem && (me & 1) == 0) ? me + 1 : me;
-    return img_store(m, count, v[src].data() - m.lo, recvbuf);
-}
-
-// Evaluate RankTree `t` on host with a user function (same association and
-// inout/in roles as k_tree: the left operand is `inout`).  x[r] = typed base of
-// rank r's contribution (count elements, image `m`); the result image is
-// written at typed base `out`.
-void eval_tree_host(const RankTree& t, const std::vector<const char*>& x, char* out, size_t count,
-                    MPI_Datatype dt, const OpRef& op, const Img& m)
-{
-    const size_t bytes = m.bytes;
-    auto call = [&](const char* in, char* io) { img_call(op, dt, m, count, in, io); };
-    auto img = [&](const char* base) { return base + m.lo; };
-    if (t.chain) {
-        memcpy(out + m.lo, img(x[(size_t)t.src[0]]), bytes);
-        for (int k = 1; k < t.P; ++k) call(x[(size_t)t.src[k]], out);
-        return;
-    }
-    const int nl = t.nleaves ? t.nleaves : t.P;
-    std::vector<std::vector<char>> v((size_t)nl);
-    for (int k = 0; k < nl; ++k) {
-        v[(size_t)k].assign(img(x[(size_t)t.src[2 * k]]), img(x[(size_t)t.src[2 * k]]) + bytes);
-        if ((t.pairmask >> k) & 1u) call(x[(size_t)t.src[2 * k + 1]], v[(size_t)k].data() - m.lo);
-    }
-    for (int w = 1; w < t.P; w *= 2)
-        for (int k = 0; k + w < t.P; k += 2 * w)
-            if (k + w < nl) call(v[(size_t)(k + w)].data() - m.lo, v[(size_t)k].data() - m.lo);
-    memcpy(out + m.lo, v[0].data(), bytes);
+    const CombinePlan plan = userop_plan(UserColl::allreduce, c->size, c->rank, op.commutative, false, count, 0);
+    return host_user_run(c, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, recvbuf, count, dt, op, &plan, 0, count, 0,
+                         count);
 }
 
 // Engine-private device scratch (grows, never shrinks; engine worker only).

@@ -182,10 +182,10 @@ Img img_of(MPI_Datatype dt, size_t count);
 int img_load(const Img& m, const void* buf, char* img);
 int img_store(const Img& m, size_t count, const char* typed_base, void* buf);
 void img_call(const OpRef& op, MPI_Datatype dt, const Img& m, size_t count, const char* in, char* io);
+int host_user_run(Comm* c, const void* src, void* recvbuf, size_t total, MPI_Datatype dt, const OpRef& op,
+                  const CombinePlan* plan, size_t first, size_t count, size_t out_first, size_t out_count);
 int host_user_allreduce(Comm* c, const void* sendbuf, void* recvbuf, size_t count,
                         MPI_Datatype dt, const OpRef& op);
-void eval_tree_host(const RankTree& t, const std::vector<const char*>& x, char* out, size_t count,
-                    MPI_Datatype dt, const OpRef& op, const Img& m);
 
 char* dev_scratch(size_t bytes);
 size_t chunk_bytes();

@@ -33,6 +33,12 @@ int real_of_newrank(int n, int p)
     return n < rem ? 2 * n + 1 : n + rem;
 }
 
+int lineage_of(int me, int p)
+{
+    const int n = newrank_of(me, p);
+    return n >= 0 ? n : newrank_of(me + 1, p);
+}
+
 Leaf leaf_of(int n, int p)
 {
     // fold: odd rank 2n+1 computes MPID_Uop_call(tmp=x_{2n}, recvbuf=x_{2n+1})
@@ -226,24 +232,141 @@ RankTree tree_pairwise(int p, int r)
     return t;
 }
 
-// The device-op collectives' evaluations (msx_devop.cpp: rd_value,
-// eval_reduce, eval_tree_dev) written as one tree each.  in_left = 0: the
-// engine's roles, left operand `inout`; in_left = 1: left operand `in`.
-//   allreduce, commutative: rd_value calls (in = partner's value, inout = own)
-//     at every step, so rank n's value is tree_allreduce of its newrank (a
-//     folded even rank takes its odd neighbour's); the fold is (in = even rank,
-//     inout = odd rank), the odd rank in slot 2k.
-//   allreduce, non-commutative: rd_value makes the lower newrank's value `in`
+// ---- the user-op collectives' combine plan (CombinePlan, msx_transport.h) ----
+// One builder per reference schedule.  Each writes the value of ONE rank as the
+// steps that compute it; a recursive builder returns the block that holds a
+// partial value, having appended the steps that produce it.
+namespace {
+struct PlanBuilder {
+    const int p;
+    const bool commutative;
+    CombinePlan plan;
+    int step(int in, int io)
+    {
+        plan.steps.push_back({in, io});
+        return io;
+    }
+
+    // Recursive doubling (reduce.cpp:3858-3925): the value of newrank n after
+    // `level` steps.  Level 0 is the fold, the even rank below 2 * rem into the
+    // odd rank above it.  At a step, a commutative op or a partner below
+    // combines Uop(partner's, own); else "the sender is above us":
+    // Uop(own, partner's) and the partner's copy takes the result.
+    int doubled(int n, int level)
+    {
+        const int r = real_of_newrank(n, p);
+        if (level == 0) return r < 2 * (p - pof2_floor(p)) ? step(r - 1, r) : r;
+        const int mask = 1 << (level - 1);
+        const int a = doubled(n, level - 1), b = doubled(n ^ mask, level - 1);
+        return (commutative || real_of_newrank(n ^ mask, p) < r) ? step(b, a) : step(a, b);
+    }
+    // rank me's allreduce value; a folded even rank gets its odd neighbour's
+    int allreduce(int me) { return doubled(lineage_of(me, p), log2i(pof2_floor(p))); }
+
+    // The binomial tree at the root (reduce.cpp:440-540): relative ranks from
+    // lroot = root (commutative) or 0; relrank rel receives from rel | mask and
+    // combines Uop(child's, own) (commutative) or Uop(own, child's), the child's
+    // copy taking the result.
+    int reduce(int root)
+    {
+        const int lroot = commutative ? root : 0;
+        std::vector<int> at((size_t)p);                      // the block holding relrank rel's value
+        for (int rel = 0; rel < p; ++rel) at[(size_t)rel] = (rel + lroot) % p;
+        for (int mask = 1; mask < p; mask <<= 1)
+            for (int rel = 0; rel + mask < p; rel += 2 * mask) {
+                int &own = at[(size_t)rel], &child = at[(size_t)(rel | mask)];
+                own = commutative ? step(child, own) : step(own, child);
+            }
+        return at[0];
+    }
+
+    // Commutative reduce_scatter (reduce.cpp:917-1334), the partner's value
+    // always `in`.  Pairwise: the blocks from ranks me - 1, me - 2, ... into
+    // the rank's own.  Recursive halving with masks P / 2, ..., 1 after the
+    // fold: a balanced tree over the leaves leaf_of(n ^ bitrev(k)) of the rank's
+    // newrank n, as tree_reduce_scatter lists them for the kernels.
+    int reduce_scatter(int me, int algo)
+    {
+        if (algo == A_RS_PAIRWISE) {
+            for (int k = 1; k < p; ++k) step(((me - k) % p + p) % p, me);
+            return me;
+        }
+        const int P = pof2_floor(p), bits = log2i(P), n = lineage_of(me, p);
+        std::vector<int> v((size_t)P);
+        for (int k = 0; k < P; ++k) {
+            const Leaf l = leaf_of(n ^ bitrev(k, bits), p);
+            v[(size_t)k] = l.b >= 0 ? step(l.b, l.a) : l.a;
+        }
+        for (int w = 1; w < P; w *= 2)
+            for (int k = 0; k + w < P; k += 2 * w) step(v[(size_t)(k + w)], v[(size_t)k]);
+        return v[0];
+    }
+
+    // Scan's recursive doubling (IscanBuildTaskList reduce.cpp:5285-5576): rank
+    // r's partial after `level` steps.  At step mask it meets r ^ mask: the rank
+    // above combines Uop(partner's, own), the rank below too when the op is
+    // commutative, else Uop(own, partner's) and the partner's copy takes the
+    // result.  The lower rank's last step feeds nothing and is not run.
+    int partial(int r, int level)
+    {
+        if (level == 0) return r;
+        const int mask = 1 << (level - 1), dst = r ^ mask;
+        const bool last = (mask << 1) >= p;
+        const int a = partial(r, level - 1);
+        if (dst >= p || (last && r < dst)) return a;
+        const int b = partial(dst, level - 1);
+        return (r > dst || commutative) ? step(b, a) : step(a, b);
+    }
+    // rank me's result: its own contribution (scan) or nothing (exscan), then
+    // Uop(partial of me ^ mask, result) at every step whose partner is below;
+    // the first such step of an exscan takes the partial itself
+    int scan(int me, bool exclusive)
+    {
+        int res = exclusive ? -1 : me, level = 0;
+        for (int mask = 1; mask < p; mask <<= 1, ++level) {
+            const int dst = me ^ mask;
+            if (dst > me) continue;
+            const int tmp = partial(dst, level);
+            res = res < 0 ? tmp : step(tmp, res);
+        }
+        return res;
+    }
+};
+}  // namespace
+
+CombinePlan userop_plan(UserColl which, int p, int n, bool commutative, bool exclusive, size_t total_count,
+                        int type_size)
+{
+    PlanBuilder b{p, commutative, {}};
+    if (which == UserColl::reduce) b.plan.result = b.reduce(n);
+    else if (which == UserColl::scan) b.plan.result = b.scan(n, exclusive);
+    else if (which == UserColl::reduce_scatter && commutative)
+        b.plan.result = b.reduce_scatter(n, reduce_scatter_algo(p, total_count, type_size, true));
+    else b.plan.result = b.allreduce(n);      // non-commutative reduce_scatter: the allreduce of the whole vector
+    return b.plan;
+}
+
+// The plans above written as one tree each, for an op with a tree function.
+// in_left = 0: the engine's roles, left operand `inout`; in_left = 1: left
+// operand `in`.
+//   allreduce, commutative: doubled() makes the partner's value `in` and the
+//     rank's own `inout` at every step, so rank n's value is tree_allreduce of
+//     its newrank (a folded even rank takes its odd neighbour's); the fold is
+//     (in = even rank, inout = odd rank), the odd rank in slot 2k.
+//   allreduce, non-commutative: doubled() makes the lower newrank's value `in`
 //     at every step, whichever rank asks: the tree over newranks 0..P-1 in
 //     order with the left operand `in`, the fold pair (even, odd) in that order.
-//   reduce: eval_reduce's binomial tree over root-relative ranks (commutative,
+//   reduce: reduce()'s binomial tree over root-relative ranks (commutative,
 //     in = right) or over ranks from 0 (non-commutative, in = left).
-//   reduce_scatter, commutative: eval_tree_dev's RankTree as it is.
-bool devop_tree_spec(int which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
+//   reduce_scatter, commutative: reduce_scatter()'s leaves are those of
+//     tree_reduce_scatter, its chain tree_pairwise.
+// tests/test_userop_plan_cpu.py evaluates both forms symbolically for every
+// shape that has a tree and requires equal expressions.
+bool devop_tree_spec(UserColl which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
                      int* in_left)
 {
     if (p < 2 || n < 0 || n >= p) return false;
-    const bool as_allreduce = which == 0 || (which == 2 && !commutative);
+    const bool as_allreduce = which == UserColl::allreduce || (which == UserColl::reduce_scatter && !commutative);
     if (as_allreduce) {
         if (p > 31) return false;
         if (commutative) {
@@ -271,13 +394,13 @@ bool devop_tree_spec(int which, int p, int n, bool commutative, size_t total_cou
         *in_left = 1;
         return true;
     }
-    if (which == 1) {
+    if (which == UserColl::reduce) {
         if (p > 16) return false;
         *t = tree_reduce_binomial(p, commutative ? n : 0);
         *in_left = commutative ? 0 : 1;
         return true;
     }
-    if (which != 2) return false;
+    if (which != UserColl::reduce_scatter) return false;
     if (reduce_scatter_algo(p, total_count, type_size, true) == A_RS_PAIRWISE) {
         if (p > 16) return false;
         *t = tree_pairwise(p, n);

@@ -122,6 +122,7 @@ struct Leaf { int a = -1, b = -1; };   // real ranks: value = a, or a op b when 
 int pof2_floor(int p);
 int newrank_of(int rank, int p);                  // -1 for folded (even, < 2*rem) ranks
 int real_of_newrank(int n, int p);
+int lineage_of(int me, int p);                    // the newrank whose value rank me gets: a folded rank's odd neighbour's
 Leaf leaf_of(int n, int p);                       // leaf value of newrank n
 int allreduce_algo(int p, size_t count, int type_size, bool builtin);
 int reduce_scatter_algo(int p, size_t total_count, int type_size, bool commutative);
@@ -163,12 +164,31 @@ RankTree tree_reduce_rsag(int p, int n);
 RankTree tree_ireduce_rsag(int p, int n, int root);
 //   reduce, binomial:     leaves x_{(k + root) % p}, k < p, of a nextpow2(p) tree
 RankTree tree_reduce_binomial(int p, int root);
-// The tree a device-op collective (msx_devop.cpp) hands to the op's tree
-// function, and its operand roles (MSX_Device_tree_function's in_left): which
-// 0 allreduce for real rank n, 1 reduce for root n, 2 reduce_scatter for real
-// rank n (total_count x type_size: the commutative gate).  false: p < 2 or the
-// shape exceeds 16 leaves, and the collective keeps its pairwise evaluation.
-bool devop_tree_spec(int which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
+// The user-op collectives (a host function or a device user op).  The values
+// are those of msx_schedule_devop_tree / msx_schedule_userop_plan.
+enum class UserColl { allreduce = 0, reduce = 1, reduce_scatter = 2, scan = 3 };
+// The value one rank gets from a user-op collective, as the pairwise calls
+// that compute it over p blocks, block r = rank r's contribution.  Every block
+// is an operand of the expression exactly once -- `in` of one step, after which
+// it is dead, or the result -- so the steps run in place on the gathered
+// blocks, with no copies.
+struct CombineStep { int in, io; };            // block io = block in (op) block io
+struct CombinePlan {
+    std::vector<CombineStep> steps;
+    int result = -1;                           // the block that holds the value; -1: none (rank 0 of an exscan)
+};
+// n: the asking rank, for reduce the root (the only rank with a value);
+// exclusive: scan only; total_count x type_size: reduce_scatter's commutative
+// gate.  Any p >= 1.  The host path (host_user_run) and the device path
+// (msx_devop.cpp) both execute this plan and nothing else.
+CombinePlan userop_plan(UserColl which, int p, int n, bool commutative, bool exclusive, size_t total_count,
+                        int type_size);
+// The same value as ONE tree, which a device-op collective hands to the op's
+// tree function, and its operand roles (MSX_Device_tree_function's in_left):
+// allreduce or reduce_scatter for real rank n, reduce for root n.  false: scan
+// (its value is not one such tree), p < 2 or a shape beyond 16 leaves, and the
+// collective runs the plan's pairwise calls.
+bool devop_tree_spec(UserColl which, int p, int n, bool commutative, size_t total_count, int type_size, RankTree* t,
                      int* in_left);
 // Bytes per element the algorithm gates multiply the count by: the blocking
 // calls use MPI_Type_size (reduce.cpp:151, :1705, :3821), the NBC task lists

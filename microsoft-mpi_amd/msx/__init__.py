@@ -178,6 +178,8 @@ def lib():
         "msx_schedule_devop_tree": (i, [i, i, i, i, i64, i, ctypes.POINTER(i), ctypes.POINTER(i),
                                         ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(i), ctypes.POINTER(i),
                                         ctypes.POINTER(i)]),
+        "msx_schedule_userop_plan": (i, [i, i, i, i, i, i64, i, ctypes.POINTER(i), i, ctypes.POINTER(i),
+                                         ctypes.POINTER(i)]),
         "msx_schedule_two_step": (i64, [i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i64), i64]),
         "msx_schedule_pieces": (i64, [i, i64, i64, i, ctypes.POINTER(i64), ctypes.POINTER(i64), i64]),
         "msx_reduce_local_multi": (i, [p, p, i64, i, i, i]),

@@ -48,6 +48,42 @@
 #define MSX_FLOAT16         ((MPI_Datatype)0x4c000250)
 #define MSX_BFLOAT16        ((MPI_Datatype)0x4c000251)
 
+/* MSX_SUM_WIDE: the fp32-accumulated tree sum of MSX_FLOAT16 / MSX_BFLOAT16
+ * (an extension: MPI_SUM on these types is defined per combine and rounds at
+ * every node).  A builtin-op handle in the 0x580000II layout with an index
+ * clear of mpi.h's (0x01 .. 0x0e); 0x50 mirrors the datatypes' choice.
+ *
+ * Definition, with w(x) and n(r) as above:
+ *   node   r = inout + in on widened values: one IEEE fp32 add, the left
+ *          operand in the `inout` role, subnormals kept -- the library's fp32
+ *          MPI_SUM combine.  A NaN r follows the x86 rule in fp32: inout's
+ *          bits | 0x00400000 if inout is a NaN, else in's bits | 0x00400000,
+ *          else 0xFFC00000.  (A 16-bit NaN widens with its sign and payload.)
+ *   tree   a fused evaluation is ONE tree of msx_reduce_tree_spec_dev's shape
+ *          (leaf pairs, balanced tree with absent leaves, or chain): the leaves
+ *          are widened, every node is computed in fp32 in the reference's
+ *          association, nothing is rounded in between;
+ *   root   n(root) is stored; for a NaN root the truncation: sign, all-ones
+ *          exponent, the top 10 (fp16) / 7 (bf16) mantissa bits.  A 16-bit NaN
+ *          comes back with its payload and the format's quiet bit, the default
+ *          NaN as 0xFE00 / 0xFFC0, and a one-source tree returns its source's
+ *          bits unchanged (signalling NaNs included).
+ * Over two sources the result equals MPI_SUM's on the same type, bit for bit.
+ *
+ * Legal with MSX_FLOAT16 and MSX_BFLOAT16 only (any other datatype:
+ * MPI_ERR_OP); commutative; MPI_Op_free refuses it; msx_op_table returns NULL
+ * (the reference's table index op % 16 - 1 cannot name it).
+ * Accepted: msx_reduce_tree_dev / _spec_dev / _done_dev; MPI_Allreduce,
+ * MPI_Reduce, MPI_Reduce_scatter[_block] and their non-blocking forms (each
+ * rank's result is one fused tree over the gathered contributions);
+ * MPI_Reduce_local, msx_reduce_local_dev and msx_reduce_local_multi (one
+ * combine: MPI_SUM's bytes).
+ * Refused with MPI_ERR_OP in the local argument checks, before any
+ * communication: MPI_Scan / MPI_Exscan / MPI_Iscan / MPI_Iexscan (their steps
+ * exchange rounded partials, so there is no fused evaluation), every one-sided
+ * call, and reductions on intercommunicators. */
+#define MSX_SUM_WIDE        ((MPI_Op)0x58000050)
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -198,7 +198,9 @@ int v_op_handle(MPI_Op op, OpRef* out)
     }
     if (handle_type(op) == HT_BUILTIN) {
         int idx = op & 0xff;
-        if (idx < O_MAX || idx > O_NOOP || (op & 0x03ffff00)) {
+        if (idx == kSumWideHandleIdx) idx = O_SUM_WIDE;      // MSX_SUM_WIDE (msx.h)
+        else if (idx > O_NOOP) idx = O_NULL;                 // no other index is a builtin op
+        if (idx < O_MAX || (op & 0x03ffff00)) {
             set_error("invalid builtin MPI_Op 0x%x", op);
             return MPI_ERR_OP;
         }
@@ -232,7 +234,22 @@ int v_no_device_op_inter(const Comm* c, const OpRef& r)
         set_error("device user ops are not supported on intercommunicators");
         return MPI_ERR_OP;
     }
+    if (c->inter && r.opidx == O_SUM_WIDE) {
+        set_error("MSX_SUM_WIDE is not supported on intercommunicators");
+        return MPI_ERR_OP;
+    }
     return MPI_SUCCESS;
+}
+
+// MSX_SUM_WIDE is defined for one fused tree over raw contributions (msx.h).
+// Calls whose steps exchange rounded partials (the scans) or combine into a
+// remote target (one-sided) refuse it here, in the local argument checks:
+// every rank fails alike, before any communication or device use.
+int v_no_sum_wide(const OpRef& r, const char* what)
+{
+    if (r.opidx != O_SUM_WIDE) return MPI_SUCCESS;
+    set_error("MSX_SUM_WIDE is not defined for %s", what);
+    return MPI_ERR_OP;
 }
 
 // MpiaOpValidate (mpi_api.h:731-775), rmaOp = false
@@ -245,7 +262,7 @@ int v_op(MPI_Op op, MPI_Datatype dt, OpRef* out)
     if (out->opidx != O_NULL) {
         rc = op_check_dtype(out->opidx, dt);
         if (rc != MPI_SUCCESS) {
-            set_error("MPI_Op 0x%x is not defined for datatype 0x%x", op, dt);
+            set_error("MPI_Op 0x%x (%s) is not defined for datatype 0x%x", op, op_name(out->opidx), dt);
             return rc;
         }
     }
@@ -968,6 +985,7 @@ int scan_common(const char* fn, const void* sendbuf, void* recvbuf, int count, M
     }
     if (rc == MPI_SUCCESS) rc = v_dtype_any(recvbuf, count, datatype);
     if (rc == MPI_SUCCESS) rc = v_op(op, datatype, &r);
+    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(r, "MPI_Scan / MPI_Exscan (their steps exchange rounded partials)");
     if (rc == MPI_SUCCESS && count > 0) {
         if (recvbuf == MPI_IN_PLACE) { set_error("recvbuf is MPI_IN_PLACE"); rc = MPI_ERR_BUFFER; }
         else if (sendbuf != MPI_IN_PLACE) {
@@ -1594,6 +1612,7 @@ int rma_op(MPI_Op op, OpRef* r, bool allow_noop)
     int rc = v_op_handle(op, r);       // MpiaOpValidate(rmaOp = true): handle only
     if (rc != MPI_SUCCESS) return rc;
     if (!allow_noop && r->opidx == O_NOOP) { set_error("MPI_NO_OP not allowed"); return MPI_ERR_OP; }
+    if ((rc = v_no_sum_wide(*r, "one-sided calls")) != MPI_SUCCESS) return rc;
     if (r->opidx == O_NULL) {
         // do_accumulate_op: **opnotpredefined (packethandling.cpp:2934-2937)
         set_error("user-defined operations are not allowed in RMA");
@@ -2443,7 +2462,9 @@ MSX_EXPORT void msx_op_replace(void* in, void* inout, int* len, MPI_Datatype* dt
 MSX_EXPORT void msx_op_noop(void*, void*, int*, MPI_Datatype*) {}
 
 // MPIR_Op_table[op % 16 - 1]: the entry of a builtin op handle
-// (MPI_MAX .. MPI_NO_OP, 0x58000001 .. 0x5800000e), NULL for anything else.
+// (MPI_MAX .. MPI_NO_OP, 0x58000001 .. 0x5800000e), NULL for anything else --
+// MSX_SUM_WIDE (0x58000050) included: op % 16 - 1 cannot name it, and a
+// pairwise entry could not keep fp32 partials between calls.
 MSX_EXPORT MPI_User_function* msx_op_table(MPI_Op op)
 {
     static MPI_User_function* const kTable[] = {

@@ -382,6 +382,9 @@ int coll_reduce_scatter(Comm* c, const void* sendbuf, void* recvbuf, const int* 
 int coll_scan(Comm* c, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt,
               const OpRef& op, bool exclusive)
 {
+    // the scan steps exchange rounded partials: no fused evaluation (msx.h);
+    // the entry points refuse it in their argument checks already
+    if (op.opidx == O_SUM_WIDE) { set_error("MSX_SUM_WIDE is not defined for MPI_Scan / MPI_Exscan"); return MPI_ERR_OP; }
     if (c->size == 1) {
         // Exscan leaves rank 0's recvbuf undefined (unchanged here).
         if (exclusive || sendbuf == MPI_IN_PLACE) return MPI_SUCCESS;

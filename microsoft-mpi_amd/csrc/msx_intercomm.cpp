@@ -295,6 +295,8 @@ int do_bcast(Comm* c, int root, char* buf, size_t bytes)
 // MPIR_Reduce_intra on inter.local_comm)
 int local_reduce0(Comm* lc, const void* sendbuf, void* recvbuf, size_t count, MPI_Datatype dt, const OpRef& op)
 {
+    // refused by the entry points (v_no_device_op_inter): this layer is frozen
+    if (op.opidx == O_SUM_WIDE) { set_error("MSX_SUM_WIDE is not supported on intercommunicators"); return MPI_ERR_OP; }
     if (lc->size == 1) return local_copy(sendbuf, recvbuf, count, dt);
     if (op.opidx == O_NULL) return host_user_reduce(lc, sendbuf, recvbuf, count, dt, op, 0);
     return do_allreduce(lc, sendbuf, recvbuf, count, dt, op, 0);

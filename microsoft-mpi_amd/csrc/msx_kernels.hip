@@ -401,6 +401,9 @@ hipError_t launch_combine(int opidx, Kind k, const void* in, void* io, size_t n,
 {
     if (n == 0) return hipSuccess;
     switch (opidx) {
+    case O_SUM_WIDE:   // one combine: widen, one fp32 add, narrow -- MPI_SUM's kernel (msx.h)
+        if (k != K_F16 && k != K_BF16) return hipErrorInvalidValue;
+        return dispatch_arith<O_SUM>(k, in, io, n, s, c);
     case O_SUM:  return dispatch_arith<O_SUM>(k, in, io, n, s, c);
     case O_MAX:  return dispatch_arith<O_MAX>(k, in, io, n, s, c);
     case O_MIN:  return dispatch_arith<O_MIN>(k, in, io, n, s, c);
@@ -477,6 +480,7 @@ hipError_t launch_tree_spec(int opidx, Kind k, const TreeSpec& t, void* out, siz
         if (t.src[0] == out) return hipSuccess;
         return hipMemcpyAsync(out, t.src[0], n * kind_size(k), hipMemcpyDeviceToDevice, s);   // xfer: device/pinned
     }
+    if (opidx == O_SUM_WIDE) return tree_dispatch_wide(k, a, ns, out, n, s);
     if (k == K_F16 || k == K_BF16) return tree_dispatch_half(opidx, k, a, ns, out, n, s);
     switch (opidx) {
     case O_SUM:    return tree_dispatch<O_SUM>(k, a, ns, out, n, s);

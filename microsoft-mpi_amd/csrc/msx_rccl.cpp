@@ -96,7 +96,7 @@ bool rccl_map(int opidx, Kind k, ncclRedOp_t* op, ncclDataType_t* t)
     case O_PROD: *op = ncclProd; break;
     case O_MAX: *op = ncclMax; break;
     case O_MIN: *op = ncclMin; break;
-    default: return false;
+    default: return false;      // O_SUM_WIDE too: its order is the engine's fused tree
     }
     switch (k) {
     case K_I8: *t = ncclInt8; return true;

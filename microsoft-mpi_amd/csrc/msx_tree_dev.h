@@ -308,8 +308,90 @@ __device__ __forceinline__ void put_vec(const TreeArgs& a, u32x4* __restrict__ o
 }
 
 template <int OP, class VT> struct VecFn {
+    static constexpr bool kWide = false;
     __device__ static u32x4 apply(u32x4 io, u32x4 in) { return apply_vec<OP, VT>(io, in); }
 };
+
+// ---- MSX_SUM_WIDE (msx.h): the fp32-accumulated tree sum of f16 / bf16 ----------
+// The tree kernels keep the 16-byte source vectors as loaded and widen an
+// element where a node consumes it; every node is the fp32 Fn<O_SUM> (one
+// v_add_f32 and the fp32 path's x86 NaN rule), walked depth first, so one
+// element holds at most log2(leaves) fp32 partials; the root is narrowed once
+// (narrow(), or the truncation of a NaN root) and packed for put_vec.
+// A tree with ONE source never gets here (tree_dispatch_wide): v_cvt_f32_f16
+// quiets a signalling NaN, which only a combine-free path could show.
+template <class H> struct VecFn<O_SUM_WIDE, H> {
+    static_assert(is_half<H>::value, "MSX_SUM_WIDE: 16-bit floats only");
+    static constexpr bool kWide = true;
+    using Elem = H;
+};
+
+// element j (0..7) of a vector of eight 16-bit floats, widened
+template <class H>
+__device__ __forceinline__ float wide_leaf(const u32x4& v, int j)
+{
+    const uint32_t w = v[j >> 1];
+    return widen(H{(uint16_t)((j & 1) ? (w >> 16) : w)});
+}
+// a NaN root truncated: sign, all-ones exponent, the top mantissa bits
+__device__ __forceinline__ uint16_t wide_nan16(uint32_t u, bf16) { return (uint16_t)(u >> 16); }
+__device__ __forceinline__ uint16_t wide_nan16(uint32_t u, f16)
+{
+    return (uint16_t)(((u >> 16) & 0x8000u) | 0x7C00u | ((u >> 13) & 0x03FFu));
+}
+template <class H>
+__device__ __forceinline__ uint16_t wide_root(float r)
+{
+    if (__builtin_expect(r == r, 1)) {
+        H o;
+        narrow(r, o);
+        return o.b;
+    }
+    return wide_nan16(__float_as_uint(r), H{});
+}
+
+// tree_fixed's tree over leaves [LO, LO + N) of element j, depth first; the
+// association, roles, pair and absent-leaf rules of tree_fixed's `reduce`
+template <class H, int LO, int N, bool MASKED>
+__device__ __forceinline__ float wide_sub(const u32x4* v, const u32x4* w, unsigned pm, int nl, int j)
+{
+    if constexpr (N == 1) {
+        float f = wide_leaf<H>(v[LO], j);
+        if constexpr (MASKED) {
+            const float g = Fn<O_SUM>::apply(f, wide_leaf<H>(w[LO], j));
+            if ((pm >> LO) & 1u) f = g;
+        }
+        return f;
+    } else {
+        const float l = wide_sub<H, LO, N / 2, MASKED>(v, w, pm, nl, j);
+        const float r = wide_sub<H, LO + N / 2, N / 2, MASKED>(v, w, pm, nl, j);
+        const float f = Fn<O_SUM>::apply(l, r);
+        if constexpr (MASKED) return (LO + N / 2 < nl) ? f : l;
+        else return f;
+    }
+}
+
+// one result vector from the raw source vectors v[0..NL) (and the fold pairs w)
+template <class H, int NL, bool CHAIN, bool MASKED>
+__device__ __forceinline__ u32x4 wide_fixed(const u32x4* v, const u32x4* w, unsigned pm, int nl)
+{
+    static_assert(CHAIN || (NL & (NL - 1)) == 0, "a tree has a power-of-two leaf count");
+    u32x4 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float f;
+        if constexpr (CHAIN) {
+            f = wide_leaf<H>(v[0], j);
+#pragma unroll
+            for (int k = 1; k < NL; ++k) f = Fn<O_SUM>::apply(f, wide_leaf<H>(v[k], j));
+        } else {
+            f = wide_sub<H, 0, NL, MASKED>(v, w, pm, nl, j);
+        }
+        const uint32_t h = wide_root<H>(f);
+        r[j >> 1] = (j & 1) ? (r[j >> 1] | (h << 16)) : h;
+    }
+    return r;
+}
 
 // The full balanced tree over NL sources (no pairs, no absent leaves: every
 // power-of-two p of the allreduce / reduce_scatter / reduce trees), or with
@@ -346,7 +428,10 @@ __device__ __forceinline__ void tree_fixed(const TreeArgs& a, u32x4* __restrict_
     const unsigned pm = MASKED ? a.pairmask : 0u;
     const int nl = MASKED ? a.nleaves : NL;
     auto reduce = [&](u32x4* v, const u32x4* w) {
-        if constexpr (CHAIN) {
+        if constexpr (F::kWide) {
+            // MSX_SUM_WIDE: fp32 partials, the raw vectors widened at use
+            return wide_fixed<typename F::Elem, NL, CHAIN, MASKED>(v, w, pm, nl);
+        } else if constexpr (CHAIN) {
 #pragma unroll
             for (int k = 1; k < NL; ++k) v[0] = F::apply(v[0], v[k]);
         } else {
@@ -413,6 +498,37 @@ __device__ __forceinline__ void tree_fixed(const TreeArgs& a, u32x4* __restrict_
     }
 }
 
+// MSX_SUM_WIDE in the generic kernel: result vector i of any tree tree_eval
+// walks.  The raw vectors of the slots the tree reads are loaded once (slot k
+// of TreeArgs::s in x[k]); tree_eval then runs per element on widened values.
+template <class H, bool NT>
+__device__ __forceinline__ u32x4 wide_eval_vec(const TreeArgs& a, size_t i)
+{
+    auto ldk = [&](int k) { return ld<NT>(reinterpret_cast<const u32x4*>(a.s[k]) + i); };
+    u32x4 x[2 * kMaxLeaves];
+    if (a.chain) {
+#pragma unroll
+        for (int k = 0; k < kMaxLeaves; ++k)
+            if (k < a.P) x[k] = ldk(k);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kMaxLeaves; ++k) {
+            if (k < a.nleaves) {
+                x[2 * k] = ldk(2 * k);
+                if ((a.pairmask >> k) & 1u) x[2 * k + 1] = ldk(2 * k + 1);
+            }
+        }
+    }
+    u32x4 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        auto load = [&](int k) { return wide_leaf<H>(x[k], j); };
+        const uint32_t h = wide_root<H>(tree_eval<Fn<O_SUM>, float>(a, load));
+        r[j >> 1] = (j & 1) ? (r[j >> 1] | (h << 16)) : h;
+    }
+    return r;
+}
+
 // The generic kernel (NL == 0: any P <= 16 tree with pairs and absent
 // leaves, any chain) loads the sources as the tree consumes them (tree_eval):
 // p = 8 fp32 SUM, 32 MiB per source, that measured 51.7 us against 57.1 us
@@ -433,16 +549,28 @@ __global__ __launch_bounds__(BLOCK) void k_tree(TreeArgs a, T* __restrict__ out,
             tree_fixed<VecFn<OP, VT>, NL, U, BLOCK, NT, CHAIN, MASKED>(a, reinterpret_cast<u32x4*>(out), nvec, bid, nb);
     } else if (vec_ok) {
         for (size_t i = bid * BLOCK + threadIdx.x; i < nvec; i += stride) {
-            auto load = [&](int k) { return ld<NT>(reinterpret_cast<const u32x4*>(a.s[k]) + i); };
-            const u32x4 r = tree_eval<VecFn<OP, VT>, u32x4>(a, load);
+            u32x4 r;
+            if constexpr (OP == O_SUM_WIDE) {
+                r = wide_eval_vec<T, NT>(a, i);
+            } else {
+                auto load = [&](int k) { return ld<NT>(reinterpret_cast<const u32x4*>(a.s[k]) + i); };
+                r = tree_eval<VecFn<OP, VT>, u32x4>(a, load);
+            }
             put_vec(a, reinterpret_cast<u32x4*>(out), i, r);
         }
     }
     const size_t first = vec_ok ? nvec * EPV : 0;
     const size_t nsc = vec_ok ? tail : tail + nvec * EPV;
     for (size_t s = (size_t)b * BLOCK + threadIdx.x; s < nsc; s += stride) {
-        auto load = [&](int k) { return reinterpret_cast<const T*>(a.s[k])[first + s]; };
-        const T r = tree_eval<Fn<OP>, T>(a, load);
+        T r;
+        if constexpr (OP == O_SUM_WIDE) {
+            // the same definition per element: fp32 nodes, one narrowing
+            auto load = [&](int k) { return widen(reinterpret_cast<const T*>(a.s[k])[first + s]); };
+            r.b = wide_root<T>(tree_eval<Fn<O_SUM>, float>(a, load));
+        } else {
+            auto load = [&](int k) { return reinterpret_cast<const T*>(a.s[k])[first + s]; };
+            r = tree_eval<Fn<OP>, T>(a, load);
+        }
         if (a.wt) {
             st_wt_elem(out + first + s, r);
             for (int e = 0; e < a.nextra; ++e) st_wt_elem(static_cast<T*>(a.extra[e]) + first + s, r);
@@ -469,5 +597,7 @@ hipError_t tree_dispatch(Kind k, const dev::TreeArgs& a, int ns, void* out, size
 // (msx_tree_half.hip), so the per-op units' compile time does not grow
 hipError_t tree_dispatch_half(int opidx, Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n,
                               hipStream_t s);
+// MSX_SUM_WIDE on K_F16 / K_BF16 (msx_tree_wide.hip): fp32 nodes, one narrowing
+hipError_t tree_dispatch_wide(Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n, hipStream_t s);
 
 }  // namespace msx

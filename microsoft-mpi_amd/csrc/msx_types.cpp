@@ -126,9 +126,19 @@ int op_legal_groups(int opidx)
         return G_CINT | G_FINT | G_BYTE | G_LOGICAL | G_PCHAR;
     case O_MAXLOC: case O_MINLOC:           // op.cpp:1543-1571
         return G_LOC;
+    case O_SUM_WIDE:                        // MSX_SUM_WIDE (msx.h): the 16-bit floats only
+        return G_HALF;
     default:
         return 0;
     }
+}
+
+const char* op_name(int opidx)
+{
+    static const char* const kNames[O_COUNT] = {
+        "MPI_OP_NULL", "MPI_MAX", "MPI_MIN", "MPI_SUM", "MPI_PROD", "MPI_LAND", "MPI_BAND", "MPI_LOR", "MPI_BOR",
+        "MPI_LXOR", "MPI_BXOR", "MPI_MINLOC", "MPI_MAXLOC", "MPI_REPLACE", "MPI_NO_OP", "MSX_SUM_WIDE"};
+    return opidx >= 0 && opidx < O_COUNT ? kNames[opidx] : "invalid op";
 }
 
 int op_check_dtype(int opidx, MPI_Datatype dt)

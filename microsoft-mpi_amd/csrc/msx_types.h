@@ -27,10 +27,15 @@ enum Kind : int {
 };
 
 // Builtin op index = HANDLE_BUILTIN_INDEX(op) (mpihandlemem.h:236), 1..14.
+// O_SUM_WIDE is MSX_SUM_WIDE (msx.h, handle index 0x50): not in the reference,
+// so it sits after O_NOOP and no reference table is indexed with it.
 enum OpIdx : int {
     O_NULL = 0, O_MAX = 1, O_MIN, O_SUM, O_PROD, O_LAND, O_BAND, O_LOR, O_BOR,
-    O_LXOR, O_BXOR, O_MINLOC, O_MAXLOC, O_REPLACE, O_NOOP, O_COUNT
+    O_LXOR, O_BXOR, O_MINLOC, O_MAXLOC, O_REPLACE, O_NOOP, O_SUM_WIDE, O_COUNT
 };
+constexpr int kSumWideHandleIdx = MSX_SUM_WIDE & 0xff;
+// name of a builtin op index for error texts ("MSX_SUM_WIDE", "MPI_SUM", ...)
+const char* op_name(int opidx);
 
 // Handle layout (src/mpi/common/mpihandlemem.h:175-236):
 //   bits 31..30 type (0 invalid, 1 builtin, 2 direct, 3 indirect)

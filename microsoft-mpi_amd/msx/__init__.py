@@ -25,7 +25,7 @@ def _parse_header_constants(path, prefix="MPI"):
     """#define NAME value / ((T)0x...) from include/mpi.h -> dict (ints only).
 
     `prefix` selects the names: MPI_* from mpi.h, MSX_* (the extension
-    datatypes MSX_FLOAT16 / MSX_BFLOAT16) from msx.h."""
+    datatypes MSX_FLOAT16 / MSX_BFLOAT16 and the op MSX_SUM_WIDE) from msx.h."""
     out = {}
     pat = re.compile(r"^#define\s+(%s_\w+)\s+(.+?)\s*(?:/\*.*)?$" % prefix)
     enum = re.compile(r"^(MPI_\w+)\s*=\s*(\d+),?$")

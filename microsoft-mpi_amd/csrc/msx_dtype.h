@@ -148,9 +148,4 @@ void dtype_delete(Dtype* t);                                   // standalone typ
 // Byte span touched by `count` instances: [lo, hi) relative to the buffer.
 void dt_span(const Dtype* t, int64_t count, int64_t* lo, int64_t* hi);
 
-// ---- entry-point helpers (msx_api.cpp) -------------------------------------
-void api_require_init(const char* fn);              // MpiaIsInitializedOrExit
-int api_err_return(const char* fn, int code);       // MPIR_Err_return_comm(NULL, ...)
-int api_comm_valid(MPI_Comm comm);                   // MpiaCommValidateHandle
-
 }  // namespace msx

@@ -14,14 +14,13 @@
 #include <vector>
 
 #include "../../include/mpi.h"
+#include "msx_api.h"
 #include "msx_comm.h"
 #include "msx_dtype.h"
 #include "msx_runtime.h"
 #include "msx_types.h"
 
 using namespace msx;
-
-#define MSX_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
@@ -639,7 +638,6 @@ MSX_EXPORT int msx_unpack_dev(const void* packed, int64_t count, MPI_Datatype da
 }
 
 // ---- PMPI_ profiling aliases --------------------------------------------------
-#define MSX_ALIAS(name) extern "C" __attribute__((visibility("default"), alias(#name)))
 MSX_ALIAS(MPI_Type_contiguous) int PMPI_Type_contiguous(int, MPI_Datatype, MPI_Datatype*);
 MSX_ALIAS(MPI_Type_vector) int PMPI_Type_vector(int, int, int, MPI_Datatype, MPI_Datatype*);
 MSX_ALIAS(MPI_Type_create_hvector) int PMPI_Type_create_hvector(int, int, MPI_Aint, MPI_Datatype, MPI_Datatype*);

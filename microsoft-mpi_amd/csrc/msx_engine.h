@@ -9,7 +9,9 @@
 //   msx_devop.cpp        the same collectives with a device-resident user op
 //   msx_rma.cpp          fence, passive-target and PSCW one-sided operations
 //   msx_intercomm.cpp    world mailbox, intercommunicators, communicator split / free
-// Never included by msx_api.cpp, msx_comm.cpp or a .hip unit: they see the
+// Never included by an entry-point unit (msx_api.cpp, msx_api_reduce.cpp,
+// msx_api_request.cpp, msx_api_rma.cpp, msx_api_ext.cpp), msx_comm.cpp or a
+// .hip unit: they see the
 // engine through msx_transport.h only.  Every piece of state named here has
 // its one definition in the .cpp that owns it.
 //

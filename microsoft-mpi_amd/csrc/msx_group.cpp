@@ -13,13 +13,12 @@
 #include <vector>
 
 #include "../../include/mpi.h"
+#include "msx_api.h"
 #include "msx_comm.h"
 #include "msx_dtype.h"
 #include "msx_runtime.h"
 
 using namespace msx;
-
-#define MSX_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace {
 
@@ -364,7 +363,6 @@ MSX_EXPORT int MPI_Group_compare(MPI_Group group1, MPI_Group group2, int* result
     return MPI_SUCCESS;
 }
 
-#define MSX_ALIAS(name) extern "C" __attribute__((visibility("default"), alias(#name)))
 MSX_ALIAS(MPI_Comm_group) int PMPI_Comm_group(MPI_Comm, MPI_Group*);
 MSX_ALIAS(MPI_Group_size) int PMPI_Group_size(MPI_Group, int*);
 MSX_ALIAS(MPI_Group_rank) int PMPI_Group_rank(MPI_Group, int*);

@@ -30,7 +30,7 @@ namespace {
 int rma_combine(const RmaDesc& d, const char* payload, char* taddr, hipStream_t s)
 {
     if (d.opidx == O_NOOP || d.count == 0) return MPI_SUCCESS;
-    // refused at the origin (rma_op, msx_api.cpp): an accumulate has no fused tree
+    // refused at the origin (rma_op, msx_api_rma.cpp): an accumulate has no fused tree
     if (d.opidx == O_SUM_WIDE) { set_error("MSX_SUM_WIDE is not defined for one-sided calls"); return MPI_ERR_OP; }
     const size_t bytes = (size_t)d.count * (size_t)d.usize;
     if (d.opidx == O_REPLACE) return copy_async(taddr, payload, bytes, s);

@@ -76,8 +76,8 @@
  * Accepted: msx_reduce_tree_dev / _spec_dev / _done_dev; MPI_Allreduce,
  * MPI_Reduce, MPI_Reduce_scatter[_block] and their non-blocking forms (each
  * rank's result is one fused tree over the gathered contributions);
- * MPI_Reduce_local, msx_reduce_local_dev and msx_reduce_local_multi (one
- * combine: MPI_SUM's bytes).
+ * MPI_Reduce_local, msx_reduce_local_dev, msx_reduce_local_batch_dev and
+ * msx_reduce_local_multi (one combine: MPI_SUM's bytes).
  * Refused with MPI_ERR_OP in the local argument checks, before any
  * communication: MPI_Scan / MPI_Exscan / MPI_Iscan / MPI_Iexscan (their steps
  * exchange rounded partials, so there is no fused evaluation), every one-sided
@@ -161,6 +161,52 @@ void msx_op_errno_reset(void);
  * stream-ordered (returns after the launch, not after completion). */
 int msx_reduce_local_dev(const void* in, void* inout, int64_t count,
                          MPI_Datatype datatype, MPI_Op op, void* stream);
+
+/* Many small combines in as few launches as possible.  in, inout and counts
+ * are HOST arrays of nseg entries; segment i is
+ *   inout[i][k] = inout[i][k] (op) in[i][k], k in [0, counts[i])
+ * on device pointers, one datatype and one op for the whole call.  The call is
+ * stream-ordered on `stream` and returns after the enqueue; the three arrays
+ * are read during the call only (the descriptors travel in the kernel
+ * arguments), so the caller may overwrite them as soon as it returns.
+ * The value: once the stream has drained, segment i holds exactly the bytes
+ * msx_reduce_local_dev(in[i], inout[i], counts[i], datatype, op, stream) would
+ * have produced, and no other byte of device memory is written.  Segments are
+ * unordered among themselves and must be independent: `in` ranges may overlap
+ * each other (one `in` may feed many segments), an `inout` range may meet no
+ * other range of the call.
+ * Builtin ops over every legal (op, predefined datatype) pair, MSX_FLOAT16 /
+ * MSX_BFLOAT16 included; MSX_SUM_WIDE is MPI_SUM's combine.  User ops, host or
+ * device, are MPI_ERR_OP.
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure:
+ *   1. nseg == 0: success;
+ *   2. nseg < 0 or a null in / inout / counts array: MPI_ERR_ARG;
+ *   3. an invalid op handle, an illegal (op, datatype) pair or a user op:
+ *      MPI_ERR_OP;
+ *   4. any counts[i] < 0: MPI_ERR_COUNT;
+ *   5. a null in[i] or inout[i] with counts[i] > 0: MPI_ERR_BUFFER (segments
+ *      with counts[i] == 0 are skipped, their pointers never looked at);
+ *   6. in[i] == inout[i], or the byte range of inout[i] meeting its own in[i]
+ *      range or any in[j] / inout[j] range, j != i: MPI_ERR_BUFFER, and
+ *      msx_last_error() names both segments;
+ *   7. no GPU: MPI_ERR_OTHER.
+ * Segments below 16 MiB per operand whose operands share one offset from
+ * 16-byte alignment are fused, up to *width per launch; operands at different
+ * offsets are fused (element by element) below 64 KiB per operand; every other
+ * segment is launched on its own, exactly as msx_reduce_local_dev launches it.
+ *
+ * msx_reduce_local_batch_plan runs checks 1 - 6 and reports what the call
+ * would do, without ever initialising a GPU (a pure function of its
+ * arguments; the addresses are never dereferenced): *width the most segments
+ * one fused launch carries, *launches the kernel launches in all, *batched the
+ * segments in fused launches, *single the segments launched on their own.
+ * Empty segments count in neither.  A null output pointer is MPI_ERR_ARG. */
+int msx_reduce_local_batch_dev(const void* const* in, void* const* inout, const int64_t* counts,
+                               int nseg, MPI_Datatype datatype, MPI_Op op, void* stream);
+int msx_reduce_local_batch_plan(const void* const* in, void* const* inout, const int64_t* counts,
+                                int nseg, MPI_Datatype datatype, MPI_Op op,
+                                int* width, int* launches, int* batched, int* single);
 
 /* Device-resident user-defined reduction ops.
  *

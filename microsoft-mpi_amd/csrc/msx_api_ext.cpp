@@ -160,6 +160,138 @@ MSX_EXPORT int msx_reduce_local_dev(const void* in, void* inout, int64_t count, 
     return reduce_local_device(r.opidx, type_info(dt)->kind, in, inout, (size_t)count, s);
 }
 
+// ---- msx_reduce_local_batch_dev: many small combines in few launches ---------
+namespace {
+// Mutually misaligned segments (operands at different offsets from 16-byte
+// alignment) run element by element inside a fused launch below this many
+// bytes per operand and take their own launch_combine (k_combine_shift) from
+// it on.
+constexpr size_t kBatchScalarMax = (size_t)64 << 10;
+
+// What one batch call does with its non-empty segments, in index order: a
+// fused segment joins the open fused launch, which is issued when it holds
+// kCombineSegsWidth segments and at the end; a single one is launched on its
+// own where it stands.
+struct BatchStep {
+    int seg;
+    bool fused;
+};
+struct BatchPlan {
+    std::vector<BatchStep> steps;
+    int fused = 0, single = 0;
+    int launches() const { return (fused + kCombineSegsWidth - 1) / kCombineSegsWidth + single; }
+};
+
+struct ByteRange {
+    uintptr_t lo, hi;
+    int seg;
+};
+
+// Checks 2-6 of msx_reduce_local_batch_dev (msx.h) and, when they pass, the
+// plan.  One function behind the plan entry and the real call.
+int batch_plan(const void* const* in, void* const* inout, const int64_t* counts, int nseg, MPI_Datatype dt, MPI_Op op,
+               OpRef* r, BatchPlan* plan)
+{
+    if (nseg < 0 || !in || !inout || !counts) { set_error("bad segment arrays (nseg=%d)", nseg); return MPI_ERR_ARG; }
+    int rc = v_op(op, dt, r);
+    if (rc != MPI_SUCCESS) return rc;
+    if (r->opidx == O_NULL || !type_info(dt)) { set_error("batch entry point takes builtin ops only"); return MPI_ERR_OP; }
+    const size_t es = (size_t)type_info(dt)->size;
+    for (int i = 0; i < nseg; ++i)
+        if (counts[i] < 0 || (uint64_t)counts[i] > (UINT64_MAX >> 1) / es) {
+            set_error("bad count of segment %d (%lld)", i, (long long)counts[i]);
+            return MPI_ERR_COUNT;
+        }
+    for (int i = 0; i < nseg; ++i)
+        if (counts[i] > 0 && (!in[i] || !inout[i])) { set_error("null buffer in segment %d", i); return MPI_ERR_BUFFER; }
+    std::vector<ByteRange> wr, rd;
+    for (int i = 0; i < nseg; ++i) {
+        if (counts[i] == 0) continue;
+        if (in[i] == inout[i]) { set_error("inbuf aliases inoutbuf in segment %d", i); return MPI_ERR_BUFFER; }
+        const size_t nb = (size_t)counts[i] * es;
+        rd.push_back({(uintptr_t)in[i], (uintptr_t)in[i] + nb, i});
+        wr.push_back({(uintptr_t)inout[i], (uintptr_t)inout[i] + nb, i});
+    }
+    // no inout range may meet another inout range or any in range: the inout
+    // ranges sorted by start are disjoint when each starts at or after the end
+    // of the one before; every in range is then looked up among them
+    std::sort(wr.begin(), wr.end(), [](const ByteRange& a, const ByteRange& b) { return a.lo < b.lo; });
+    for (size_t j = 1; j < wr.size(); ++j)
+        if (wr[j].lo < wr[j - 1].hi) {
+            set_error("inout of segment %d overlaps inout of segment %d", wr[j].seg, wr[j - 1].seg);
+            return MPI_ERR_BUFFER;
+        }
+    for (const ByteRange& x : rd) {
+        auto w = std::upper_bound(wr.begin(), wr.end(), x.lo, [](uintptr_t v, const ByteRange& b) { return v < b.hi; });
+        if (w != wr.end() && w->lo < x.hi) {
+            set_error("inout of segment %d overlaps in of segment %d", w->seg, x.seg);
+            return MPI_ERR_BUFFER;
+        }
+    }
+    for (int i = 0; i < nseg; ++i) {
+        if (counts[i] == 0) continue;
+        const size_t nb = (size_t)counts[i] * es;
+        const bool apart = ((uintptr_t)in[i] & 15) != ((uintptr_t)inout[i] & 15);
+        const bool fused = nb < kCombineSegsMaxBytes && !(apart && nb >= kBatchScalarMax);
+        plan->steps.push_back({i, fused});
+        ++(fused ? plan->fused : plan->single);
+    }
+    return MPI_SUCCESS;
+}
+}  // namespace
+
+MSX_EXPORT int msx_reduce_local_batch_plan(const void* const* in, void* const* inout, const int64_t* counts, int nseg,
+                                           MPI_Datatype dt, MPI_Op op, int* width, int* launches, int* batched,
+                                           int* single)
+{
+    if (!width || !launches || !batched || !single) { set_error("null plan output"); return MPI_ERR_ARG; }
+    *width = kCombineSegsWidth;
+    *launches = *batched = *single = 0;
+    if (nseg == 0) return MPI_SUCCESS;
+    OpRef r;
+    BatchPlan plan;
+    const int rc = batch_plan(in, inout, counts, nseg, dt, op, &r, &plan);
+    if (rc != MPI_SUCCESS) return rc;
+    *launches = plan.launches();
+    *batched = plan.fused;
+    *single = plan.single;
+    return MPI_SUCCESS;
+}
+
+MSX_EXPORT int msx_reduce_local_batch_dev(const void* const* in, void* const* inout, const int64_t* counts, int nseg,
+                                          MPI_Datatype dt, MPI_Op op, void* stream)
+{
+    if (nseg == 0) return MPI_SUCCESS;
+    OpRef r;
+    BatchPlan plan;
+    int rc = batch_plan(in, inout, counts, nseg, dt, op, &r, &plan);
+    if (rc != MPI_SUCCESS) return rc;
+    if (plan.steps.empty()) return MPI_SUCCESS;         // every segment empty
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the HIP null stream
+    const Kind k = type_info(dt)->kind;
+    CombineSeg segs[kCombineSegsWidth];
+    int n = 0, left = plan.fused;
+    for (const BatchStep& st : plan.steps) {
+        const int i = st.seg;
+        if (!st.fused) {
+            // large and far-misaligned segments: launch_combine's own kernels and geometry
+            rc = reduce_local_device(r.opidx, k, in[i], inout[i], (size_t)counts[i], s);
+            if (rc != MPI_SUCCESS) return rc;
+            continue;
+        }
+        segs[n++] = CombineSeg{in[i], inout[i], (size_t)counts[i]};
+        if (n == kCombineSegsWidth || n == left) {
+            hipError_t e = launch_combine_segs(r.opidx, k, segs, n, s);
+            if (e != hipSuccess) return hip_fail(e, "batch combine kernel launch");
+            left -= n;
+            n = 0;
+        }
+    }
+    return MPI_SUCCESS;
+}
+
 // one MPI_Reduce_local-sized vector split over the node's GPUs
 // (ngpus <= 0: all visible), host operands over each GPU's own PCIe link;
 // MPI_Reduce_local's checks, error codes returned (no error handler).

@@ -31,6 +31,20 @@ struct LaunchCfg {
 hipError_t launch_combine(int opidx, Kind k, const void* in, void* inout, size_t count,
                           hipStream_t s, const LaunchCfg& cfg);
 
+// Many independent combines of one (op, kind) in ONE launch (k_combine_segs,
+// msx_combine_segs.hip): segment i is inout[i] = op(inout[i], in[i]) over
+// `count` elements, the bytes launch_combine gives.  At most
+// kCombineSegsWidth segments, each below kCombineSegsMaxBytes per operand
+// (larger ones keep launch_combine's own kernels); empty segments are skipped.
+constexpr int kCombineSegsWidth = 128;
+constexpr size_t kCombineSegsMaxBytes = (size_t)16 << 20;
+struct CombineSeg {
+    const void* in;
+    void* io;
+    size_t count;
+};
+hipError_t launch_combine_segs(int opidx, Kind k, const CombineSeg* segs, int nseg, hipStream_t s);
+
 // Reference-order tree combine over p inputs (p = 1..8):
 //   out[i] = T(srcs[0][i], ..., srcs[p-1][i]) where T is the balanced binary
 //   tree of the reference's recursive-halving/doubling schedules with the

@@ -186,6 +186,10 @@ def lib():
         "msx_reduce_tree_spec_dev": (i, [ctypes.POINTER(p), i, ctypes.c_uint, i, i, p, i64, i, i, p]),
         "msx_type_size": (i, [i]),
         "msx_reduce_local_dev": (i, [p, p, i64, i, i, p]),
+        # host arrays of device pointers / counts as void*
+        "msx_reduce_local_batch_dev": (i, [p, p, p, i, i, i, p]),
+        "msx_reduce_local_batch_plan": (i, [p, p, p, i, i, i, ctypes.POINTER(i), ctypes.POINTER(i),
+                                            ctypes.POINTER(i), ctypes.POINTER(i)]),
         "msx_pack_dev": (i, [p, i64, i, p, p]),
         "msx_unpack_dev": (i, [p, i64, i, p, p]),
         "msx_reduce_tree_dev": (i, [ctypes.POINTER(p), i, p, i64, i, i, p]),

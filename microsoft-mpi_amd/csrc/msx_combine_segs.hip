@@ -13,6 +13,7 @@
 
 #include "msx_combine_dev.h"
 #include "msx_kernels.h"
+#include "msx_op_kind.h"
 
 namespace msx {
 namespace dev {
@@ -116,75 +117,19 @@ hipError_t segs_bitwise(Kind k, const CombineSeg* g, int n, hipStream_t s)
     return run_segs<OP, uint8_t, uint32_t>(g, n, (size_t)kind_size(k), s);
 }
 
-// The (op, kind) set of launch_combine's switch (msx_kernels.hip).
-template <int OP>
-hipError_t segs_arith(Kind k, const CombineSeg* g, int n, hipStream_t s)
-{
-    switch (k) {
-    case K_I8:  return segs_default<OP, int8_t>(g, n, s);
-    case K_U8:  return segs_default<OP, uint8_t>(g, n, s);
-    case K_I16: return segs_default<OP, int16_t>(g, n, s);
-    case K_U16: return segs_default<OP, uint16_t>(g, n, s);
-    case K_I32: return segs_default<OP, int32_t>(g, n, s);
-    case K_U32: return segs_default<OP, uint32_t>(g, n, s);
-    case K_I64: return segs_default<OP, int64_t>(g, n, s);
-    case K_U64: return segs_default<OP, uint64_t>(g, n, s);
-    case K_F32: return segs_default<OP, float>(g, n, s);
-    case K_F64: return segs_default<OP, double>(g, n, s);
-    default: break;
-    }
-    if constexpr (OP == O_SUM || OP == O_PROD) {
-        if (k == K_C32) return segs_default<OP, c32>(g, n, s);
-        if (k == K_C64) return segs_default<OP, c64>(g, n, s);
-    }
-    if constexpr (OP == O_LAND || OP == O_LOR || OP == O_LXOR) {
-        if (k == K_BOOL) return segs_default<OP, uint8_t>(g, n, s);
-    }
-    if constexpr (OP == O_SUM || OP == O_PROD || OP == O_MAX || OP == O_MIN) {
-        if (k == K_F16) return segs_default<OP, f16>(g, n, s);
-        if (k == K_BF16) return segs_default<OP, bf16>(g, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int OP>
-hipError_t segs_loc(Kind k, const CombineSeg* g, int n, hipStream_t s)
-{
-    switch (k) {
-    case K_LOC_II: return segs_default<OP, loc_ii>(g, n, s);
-    case K_LOC_FI: return segs_default<OP, loc_fi>(g, n, s);
-    case K_LOC_SI: return segs_default<OP, loc_si>(g, n, s);
-    case K_LOC_DI: return segs_default<OP, loc_di>(g, n, s);
-    case K_LOC_FF: return segs_default<OP, loc_ff>(g, n, s);
-    case K_LOC_DD: return segs_default<OP, loc_dd>(g, n, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_combine_segs(int opidx, Kind k, const CombineSeg* g, int n, hipStream_t s)
 {
     if (n < 0 || n > kCombineSegsWidth || (n > 0 && !g)) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    switch (opidx) {
-    case O_SUM_WIDE:   // one combine: MPI_SUM's kernel, as launch_combine
-        if (k != K_F16 && k != K_BF16) return hipErrorInvalidValue;
-        return segs_arith<O_SUM>(k, g, n, s);
-    case O_SUM:  return segs_arith<O_SUM>(k, g, n, s);
-    case O_MAX:  return segs_arith<O_MAX>(k, g, n, s);
-    case O_MIN:  return segs_arith<O_MIN>(k, g, n, s);
-    case O_PROD: return segs_arith<O_PROD>(k, g, n, s);
-    case O_LAND: return segs_arith<O_LAND>(k, g, n, s);
-    case O_LOR:  return segs_arith<O_LOR>(k, g, n, s);
-    case O_LXOR: return segs_arith<O_LXOR>(k, g, n, s);
-    case O_BAND: return segs_bitwise<O_BAND>(k, g, n, s);
-    case O_BOR:  return segs_bitwise<O_BOR>(k, g, n, s);
-    case O_BXOR: return segs_bitwise<O_BXOR>(k, g, n, s);
-    case O_MAXLOC: return segs_loc<O_MAXLOC>(k, g, n, s);
-    case O_MINLOC: return segs_loc<O_MINLOC>(k, g, n, s);
-    default: return hipErrorInvalidValue;
-    }
+    return for_op(single_combine_op(opidx, k), [&](auto op) {
+        constexpr int OP = decltype(op)::value;
+        if constexpr (op_bytewise(OP))
+            return segs_bitwise<OP>(k, g, n, s);
+        else
+            return for_kind<OP>(k, [&](auto t) { return segs_default<OP, typename decltype(t)::type>(g, n, s); });
+    });
 }
 
 }  // namespace msx

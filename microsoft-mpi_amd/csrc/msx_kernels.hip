@@ -23,6 +23,7 @@
 
 #include "msx_combine_dev.h"
 #include "msx_kernels.h"
+#include "msx_op_kind.h"
 
 namespace msx {
 namespace dev {
@@ -348,76 +349,21 @@ hipError_t run_bitwise(const void* in, void* io, size_t nbytes, hipStream_t s, c
     return run_combine<OP, uint8_t, uint32_t, kUnroll, kBlock, true, false>(in, io, nbytes, s, cfg);
 }
 
-template <int OP>
-hipError_t dispatch_arith(Kind k, const void* in, void* io, size_t n, hipStream_t s,
-                          const LaunchCfg& c)
-{
-    switch (k) {
-    case K_I8:  return run_default<OP, int8_t>(in, io, n, s, c);
-    case K_U8:  return run_default<OP, uint8_t>(in, io, n, s, c);
-    case K_I16: return run_default<OP, int16_t>(in, io, n, s, c);
-    case K_U16: return run_default<OP, uint16_t>(in, io, n, s, c);
-    case K_I32: return run_default<OP, int32_t>(in, io, n, s, c);
-    case K_U32: return run_default<OP, uint32_t>(in, io, n, s, c);
-    case K_I64: return run_default<OP, int64_t>(in, io, n, s, c);
-    case K_U64: return run_default<OP, uint64_t>(in, io, n, s, c);
-    case K_F32: return run_default<OP, float>(in, io, n, s, c);
-    case K_F64: return run_default<OP, double>(in, io, n, s, c);
-    default: break;
-    }
-    if constexpr (OP == O_SUM || OP == O_PROD) {
-        if (k == K_C32) return run_default<OP, c32>(in, io, n, s, c);
-        if (k == K_C64) return run_default<OP, c64>(in, io, n, s, c);
-    }
-    if constexpr (OP == O_LAND || OP == O_LOR || OP == O_LXOR) {
-        if (k == K_BOOL) return run_default<OP, uint8_t>(in, io, n, s, c);
-    }
-    if constexpr (OP == O_SUM || OP == O_PROD || OP == O_MAX || OP == O_MIN) {
-        if (k == K_F16) return run_default<OP, f16>(in, io, n, s, c);
-        if (k == K_BF16) return run_default<OP, bf16>(in, io, n, s, c);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int OP>
-hipError_t dispatch_loc(Kind k, const void* in, void* io, size_t n, hipStream_t s,
-                        const LaunchCfg& c)
-{
-    switch (k) {
-    case K_LOC_II: return run_default<OP, loc_ii>(in, io, n, s, c);
-    case K_LOC_FI: return run_default<OP, loc_fi>(in, io, n, s, c);
-    case K_LOC_SI: return run_default<OP, loc_si>(in, io, n, s, c);
-    case K_LOC_DI: return run_default<OP, loc_di>(in, io, n, s, c);
-    case K_LOC_FF: return run_default<OP, loc_ff>(in, io, n, s, c);
-    case K_LOC_DD: return run_default<OP, loc_dd>(in, io, n, s, c);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_combine(int opidx, Kind k, const void* in, void* io, size_t n, hipStream_t s,
                           const LaunchCfg& c)
 {
     if (n == 0) return hipSuccess;
-    switch (opidx) {
-    case O_SUM_WIDE:   // one combine: widen, one fp32 add, narrow -- MPI_SUM's kernel (msx.h)
-        if (k != K_F16 && k != K_BF16) return hipErrorInvalidValue;
-        return dispatch_arith<O_SUM>(k, in, io, n, s, c);
-    case O_SUM:  return dispatch_arith<O_SUM>(k, in, io, n, s, c);
-    case O_MAX:  return dispatch_arith<O_MAX>(k, in, io, n, s, c);
-    case O_MIN:  return dispatch_arith<O_MIN>(k, in, io, n, s, c);
-    case O_PROD: return dispatch_arith<O_PROD>(k, in, io, n, s, c);
-    case O_LAND: return dispatch_arith<O_LAND>(k, in, io, n, s, c);
-    case O_LOR:  return dispatch_arith<O_LOR>(k, in, io, n, s, c);
-    case O_LXOR: return dispatch_arith<O_LXOR>(k, in, io, n, s, c);
-    case O_BAND: return run_bitwise<O_BAND>(in, io, n * kind_size(k), s, c);
-    case O_BOR:  return run_bitwise<O_BOR>(in, io, n * kind_size(k), s, c);
-    case O_BXOR: return run_bitwise<O_BXOR>(in, io, n * kind_size(k), s, c);
-    case O_MAXLOC: return dispatch_loc<O_MAXLOC>(k, in, io, n, s, c);
-    case O_MINLOC: return dispatch_loc<O_MINLOC>(k, in, io, n, s, c);
-    default: return hipErrorInvalidValue;
-    }
+    return for_op(single_combine_op(opidx, k), [&](auto op) {
+        constexpr int OP = decltype(op)::value;
+        if constexpr (op_bytewise(OP))
+            return run_bitwise<OP>(in, io, n * kind_size(k), s, c);
+        else
+            return for_kind<OP>(k, [&](auto t) {
+                return run_default<OP, typename decltype(t)::type>(in, io, n, s, c);
+            });
+    });
 }
 
 hipError_t launch_tree(int opidx, Kind k, const void* const* srcs, int p, void* out, size_t n,
@@ -482,21 +428,7 @@ hipError_t launch_tree_spec(int opidx, Kind k, const TreeSpec& t, void* out, siz
     }
     if (opidx == O_SUM_WIDE) return tree_dispatch_wide(k, a, ns, out, n, s);
     if (k == K_F16 || k == K_BF16) return tree_dispatch_half(opidx, k, a, ns, out, n, s);
-    switch (opidx) {
-    case O_SUM:    return tree_dispatch<O_SUM>(k, a, ns, out, n, s);
-    case O_MAX:    return tree_dispatch<O_MAX>(k, a, ns, out, n, s);
-    case O_MIN:    return tree_dispatch<O_MIN>(k, a, ns, out, n, s);
-    case O_PROD:   return tree_dispatch<O_PROD>(k, a, ns, out, n, s);
-    case O_LAND:   return tree_dispatch<O_LAND>(k, a, ns, out, n, s);
-    case O_LOR:    return tree_dispatch<O_LOR>(k, a, ns, out, n, s);
-    case O_LXOR:   return tree_dispatch<O_LXOR>(k, a, ns, out, n, s);
-    case O_BAND:   return tree_dispatch<O_BAND>(k, a, ns, out, n, s);
-    case O_BOR:    return tree_dispatch<O_BOR>(k, a, ns, out, n, s);
-    case O_BXOR:   return tree_dispatch<O_BXOR>(k, a, ns, out, n, s);
-    case O_MAXLOC: return tree_dispatch<O_MAXLOC>(k, a, ns, out, n, s);
-    case O_MINLOC: return tree_dispatch<O_MINLOC>(k, a, ns, out, n, s);
-    default: return hipErrorInvalidValue;
-    }
+    return for_op(opidx, [&](auto op) { return tree_dispatch<decltype(op)::value>(k, a, ns, out, n, s); });
 }
 
 unsigned long long flag_wait_ticks()

@@ -22,6 +22,7 @@
 #include "msx_dev_ops.h"
 #include "msx_dtype.h"
 #include "msx_kernels.h"
+#include "msx_op_kind.h"
 
 namespace msx {
 namespace dev {
@@ -398,70 +399,26 @@ hipError_t copy_g(int G, const CopyArgs& a, bool reg, hipStream_t s)
     }
 }
 
-// Which (op, element) pairs have a kernel: the builtin ops' tables (op.cpp:739-1883).
-template <int OP, class T> struct AccLegal {
-    static constexpr bool arith = std::is_arithmetic<T>::value;
-    static constexpr bool value =
-        ((OP == O_MAX || OP == O_MIN || OP == O_SUM || OP == O_PROD) && is_half<T>::value) ||
-        ((OP == O_MAX || OP == O_MIN || OP == O_LAND || OP == O_LOR || OP == O_LXOR) && arith) ||
-        ((OP == O_SUM || OP == O_PROD) && (arith || std::is_same<T, c32>::value || std::is_same<T, c64>::value)) ||
-        ((OP == O_BAND || OP == O_BOR || OP == O_BXOR) && std::is_integral<T>::value) ||
-        ((OP == O_MAXLOC || OP == O_MINLOC) &&
-         (std::is_same<T, loc_ii>::value || std::is_same<T, loc_fi>::value || std::is_same<T, loc_si>::value ||
-          std::is_same<T, loc_di>::value || std::is_same<T, loc_ff>::value || std::is_same<T, loc_dd>::value));
-};
-
+// One (op, element type) pair of msx_op_kind.h's map.
 template <int OP, class T>
 hipError_t run_acc(const DevLayout& L, int64_t count, const void* packed, void* typed, hipStream_t s)
 {
-    if constexpr (!AccLegal<OP, T>::value) {
-        return hipErrorInvalidValue;
-    } else {
-        constexpr int E = (int)sizeof(T);
-        // every run offset / length must hold whole elements for the element map
-        if (L.size % E) return hipErrorInvalidValue;
-        CopyArgs a = make_args(L, count, typed, const_cast<void*>(packed), E);
-        if (L.regular && (L.blen % E)) return hipErrorInvalidValue;
-        const bool aligned = L.align >= (int)alignof(T);
-        const bool reg = L.regular != 0;
-        const int64_t tiles = (a.ngran + 64 * kUnroll - 1) / (64 * kUnroll);
-        if (tiles == 0) return hipSuccess;
-        if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
-        const dim3 tg((unsigned)tiles), tb(64);
-        if (reg && aligned) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, true, true>), tg, tb, 0, s, a);
-        else if (reg) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, true, false>), tg, tb, 0, s, a);
-        else if (aligned) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, false, true>), tg, tb, 0, s, a);
-        else hipLaunchKernelGGL((k_dt_acc_tile<OP, T, false, false>), tg, tb, 0, s, a);
-        return hipGetLastError();
-    }
-}
-
-template <int OP>
-hipError_t acc_kind(Kind k, const DevLayout& L, int64_t count, const void* packed, void* typed, hipStream_t s)
-{
-    switch (k) {
-    case K_I8: return run_acc<OP, int8_t>(L, count, packed, typed, s);
-    case K_U8: case K_BOOL: return run_acc<OP, uint8_t>(L, count, packed, typed, s);
-    case K_I16: return run_acc<OP, int16_t>(L, count, packed, typed, s);
-    case K_U16: return run_acc<OP, uint16_t>(L, count, packed, typed, s);
-    case K_I32: return run_acc<OP, int32_t>(L, count, packed, typed, s);
-    case K_U32: return run_acc<OP, uint32_t>(L, count, packed, typed, s);
-    case K_I64: return run_acc<OP, int64_t>(L, count, packed, typed, s);
-    case K_U64: return run_acc<OP, uint64_t>(L, count, packed, typed, s);
-    case K_F32: return run_acc<OP, float>(L, count, packed, typed, s);
-    case K_F64: return run_acc<OP, double>(L, count, packed, typed, s);
-    case K_C32: return run_acc<OP, c32>(L, count, packed, typed, s);
-    case K_C64: return run_acc<OP, c64>(L, count, packed, typed, s);
-    case K_LOC_II: return run_acc<OP, loc_ii>(L, count, packed, typed, s);
-    case K_LOC_FI: return run_acc<OP, loc_fi>(L, count, packed, typed, s);
-    case K_LOC_SI: return run_acc<OP, loc_si>(L, count, packed, typed, s);
-    case K_LOC_DI: return run_acc<OP, loc_di>(L, count, packed, typed, s);
-    case K_LOC_FF: return run_acc<OP, loc_ff>(L, count, packed, typed, s);
-    case K_LOC_DD: return run_acc<OP, loc_dd>(L, count, packed, typed, s);
-    case K_F16: return run_acc<OP, f16>(L, count, packed, typed, s);
-    case K_BF16: return run_acc<OP, bf16>(L, count, packed, typed, s);
-    default: return hipErrorInvalidValue;
-    }
+    constexpr int E = (int)sizeof(T);
+    // every run offset / length must hold whole elements for the element map
+    if (L.size % E) return hipErrorInvalidValue;
+    CopyArgs a = make_args(L, count, typed, const_cast<void*>(packed), E);
+    if (L.regular && (L.blen % E)) return hipErrorInvalidValue;
+    const bool aligned = L.align >= (int)alignof(T);
+    const bool reg = L.regular != 0;
+    const int64_t tiles = (a.ngran + 64 * kUnroll - 1) / (64 * kUnroll);
+    if (tiles == 0) return hipSuccess;
+    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
+    const dim3 tg((unsigned)tiles), tb(64);
+    if (reg && aligned) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, true, true>), tg, tb, 0, s, a);
+    else if (reg) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, true, false>), tg, tb, 0, s, a);
+    else if (aligned) hipLaunchKernelGGL((k_dt_acc_tile<OP, T, false, true>), tg, tb, 0, s, a);
+    else hipLaunchKernelGGL((k_dt_acc_tile<OP, T, false, false>), tg, tb, 0, s, a);
+    return hipGetLastError();
 }
 
 }  // namespace dev
@@ -481,22 +438,12 @@ hipError_t launch_dt_acc(int opidx, Kind k, const DevLayout& L, int64_t count, c
                          void* typed, hipStream_t s)
 {
     if (count <= 0 || L.size == 0) return hipSuccess;
-    switch (opidx) {
-    case O_MAX: return dev::acc_kind<O_MAX>(k, L, count, packed, typed, s);
-    case O_MIN: return dev::acc_kind<O_MIN>(k, L, count, packed, typed, s);
-    case O_SUM: return dev::acc_kind<O_SUM>(k, L, count, packed, typed, s);
-    case O_PROD: return dev::acc_kind<O_PROD>(k, L, count, packed, typed, s);
-    case O_LAND: return dev::acc_kind<O_LAND>(k, L, count, packed, typed, s);
-    case O_BAND: return dev::acc_kind<O_BAND>(k, L, count, packed, typed, s);
-    case O_LOR: return dev::acc_kind<O_LOR>(k, L, count, packed, typed, s);
-    case O_BOR: return dev::acc_kind<O_BOR>(k, L, count, packed, typed, s);
-    case O_LXOR: return dev::acc_kind<O_LXOR>(k, L, count, packed, typed, s);
-    case O_BXOR: return dev::acc_kind<O_BXOR>(k, L, count, packed, typed, s);
-    case O_MINLOC: return dev::acc_kind<O_MINLOC>(k, L, count, packed, typed, s);
-    case O_MAXLOC: return dev::acc_kind<O_MAXLOC>(k, L, count, packed, typed, s);
-    case O_REPLACE: return launch_dt_copy(L, count, typed, const_cast<void*>(packed), true, s);
-    default: return hipErrorInvalidValue;
-    }
+    if (opidx == O_REPLACE) return launch_dt_copy(L, count, typed, const_cast<void*>(packed), true, s);
+    return for_op(opidx, [&](auto op) {
+        return for_kind<decltype(op)::value>(k, [&](auto t) {
+            return dev::run_acc<decltype(op)::value, typename decltype(t)::type>(L, count, packed, typed, s);
+        });
+    });
 }
 
 }  // namespace msx

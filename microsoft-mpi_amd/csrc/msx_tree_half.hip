@@ -5,28 +5,16 @@
 #include "msx_tree_impl.h"
 
 namespace msx {
-namespace {
-
-template <int OP>
-hipError_t tree_half(Kind k, const TreeArgs& a, int ns, void* out, size_t n, hipStream_t s)
-{
-    if (k == K_F16) return run_tree_auto<OP, f16, f16>(a, ns, out, n, s);
-    if (k == K_BF16) return run_tree_auto<OP, bf16, bf16>(a, ns, out, n, s);
-    return hipErrorInvalidValue;
-}
-
-}  // namespace
 
 hipError_t tree_dispatch_half(int opidx, Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n,
                               hipStream_t s)
 {
-    switch (opidx) {
-    case O_SUM:  return tree_half<O_SUM>(k, a, ns, out, n, s);
-    case O_PROD: return tree_half<O_PROD>(k, a, ns, out, n, s);
-    case O_MAX:  return tree_half<O_MAX>(k, a, ns, out, n, s);
-    case O_MIN:  return tree_half<O_MIN>(k, a, ns, out, n, s);
-    default: return hipErrorInvalidValue;
-    }
+    return for_op(opidx, [&](auto op) {
+        return for_kind<decltype(op)::value, C_HALF>(k, [&](auto t) {
+            using T = typename decltype(t)::type;
+            return run_tree_auto<decltype(op)::value, T, T>(a, ns, out, n, s);
+        });
+    });
 }
 
 }  // namespace msx

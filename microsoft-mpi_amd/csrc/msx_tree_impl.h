@@ -3,6 +3,7 @@
 // bit.hip), so the template instantiations compile in parallel.  Included by
 // those files only.
 #pragma once
+#include "msx_op_kind.h"
 #include "msx_tree_dev.h"
 
 namespace msx {
@@ -120,57 +121,18 @@ hipError_t run_tree_auto(const TreeArgs& a, int nsrc, void* out, size_t count, h
     return run_tree_sel<OP, T, VT, U, false>(a, nsrc, out, count, s);
 }
 
-template <int OP>
-hipError_t tree_arith(Kind k, const TreeArgs& a, int ns, void* out, size_t n, hipStream_t s)
-{
-    switch (k) {
-    case K_I8:  return run_tree_auto<OP, int8_t, int8_t>(a, ns, out, n, s);
-    case K_U8:  return run_tree_auto<OP, uint8_t, uint8_t>(a, ns, out, n, s);
-    case K_I16: return run_tree_auto<OP, int16_t, int16_t>(a, ns, out, n, s);
-    case K_U16: return run_tree_auto<OP, uint16_t, uint16_t>(a, ns, out, n, s);
-    case K_I32: return run_tree_auto<OP, int32_t, int32_t>(a, ns, out, n, s);
-    case K_U32: return run_tree_auto<OP, uint32_t, uint32_t>(a, ns, out, n, s);
-    case K_I64: return run_tree_auto<OP, int64_t, int64_t>(a, ns, out, n, s);
-    case K_U64: return run_tree_auto<OP, uint64_t, uint64_t>(a, ns, out, n, s);
-    case K_F32: return run_tree_auto<OP, float, float>(a, ns, out, n, s);
-    case K_F64: return run_tree_auto<OP, double, double>(a, ns, out, n, s);
-    default: break;
-    }
-    if constexpr (OP == O_SUM || OP == O_PROD) {
-        if (k == K_C32) return run_tree_auto<OP, c32, c32>(a, ns, out, n, s);
-        if (k == K_C64) return run_tree_auto<OP, c64, c64>(a, ns, out, n, s);
-    }
-    if constexpr (OP == O_LAND || OP == O_LOR || OP == O_LXOR) {
-        if (k == K_BOOL) return run_tree_auto<OP, uint8_t, uint8_t>(a, ns, out, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int OP>
-hipError_t tree_loc(Kind k, const TreeArgs& a, int ns, void* out, size_t n, hipStream_t s)
-{
-    switch (k) {
-    case K_LOC_II: return run_tree_auto<OP, loc_ii, loc_ii>(a, ns, out, n, s);
-    case K_LOC_FI: return run_tree_auto<OP, loc_fi, loc_fi>(a, ns, out, n, s);
-    case K_LOC_SI: return run_tree_auto<OP, loc_si, loc_si>(a, ns, out, n, s);
-    case K_LOC_DI: return run_tree_auto<OP, loc_di, loc_di>(a, ns, out, n, s);
-    case K_LOC_FF: return run_tree_auto<OP, loc_ff, loc_ff>(a, ns, out, n, s);
-    case K_LOC_DD: return run_tree_auto<OP, loc_dd, loc_dd>(a, ns, out, n, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 template <int OP>
 hipError_t tree_dispatch(Kind k, const TreeArgs& a, int ns, void* out, size_t n, hipStream_t s)
 {
-    if constexpr (OP == O_BAND || OP == O_BOR || OP == O_BXOR)     // raw bytes on 32-bit lanes
+    if constexpr (op_bytewise(OP))     // raw bytes on 32-bit lanes
         return run_tree_auto<OP, uint8_t, uint32_t>(a, ns, out, n * kind_size(k), s);
-    else if constexpr (OP == O_MAXLOC || OP == O_MINLOC)
-        return tree_loc<OP>(k, a, ns, out, n, s);
-    else
-        return tree_arith<OP>(k, a, ns, out, n, s);
+    else      // the 16-bit floats are msx_tree_half.hip's
+        return for_kind<OP, C_ALL & ~C_HALF>(k, [&](auto t) {
+            using T = typename decltype(t)::type;
+            return run_tree_auto<OP, T, T>(a, ns, out, n, s);
+        });
 }
 
 }  // namespace msx

@@ -9,15 +9,17 @@ namespace msx {
 
 hipError_t tree_dispatch_wide(Kind k, const dev::TreeArgs& a, int ns, void* out, size_t n, hipStream_t s)
 {
-    if (k != K_F16 && k != K_BF16) return hipErrorInvalidValue;
-    // One source and no combine (a chain of one, a tree whose only leaf has no
-    // pair): the result is the source's bits, signalling NaNs included.  The
-    // per-node kernel copies them (no node runs, so the op does not matter)
-    // with the same extra destinations and result-ready count.
-    if (a.chain ? a.P == 1 : (a.nleaves == 1 && (a.pairmask & 1u) == 0))
-        return tree_dispatch_half(O_SUM, k, a, ns, out, n, s);
-    if (k == K_F16) return run_tree_auto<O_SUM_WIDE, f16, f16>(a, ns, out, n, s);
-    return run_tree_auto<O_SUM_WIDE, bf16, bf16>(a, ns, out, n, s);
+    // the kinds of MPI_SUM's 16-bit floats
+    return for_kind<O_SUM, C_HALF>(k, [&](auto t) {
+        using T = typename decltype(t)::type;
+        // One source and no combine (a chain of one, a tree whose only leaf has no
+        // pair): the result is the source's bits, signalling NaNs included.  The
+        // per-node kernel copies them (no node runs, so the op does not matter)
+        // with the same extra destinations and result-ready count.
+        if (a.chain ? a.P == 1 : (a.nleaves == 1 && (a.pairmask & 1u) == 0))
+            return tree_dispatch_half(O_SUM, k, a, ns, out, n, s);
+        return run_tree_auto<O_SUM_WIDE, T, T>(a, ns, out, n, s);
+    });
 }
 
 }  // namespace msx

@@ -86,6 +86,12 @@ const TypeInfo* type_info(MPI_Datatype dt)
     return nullptr;
 }
 
+const TypeInfo* type_table(int* n)
+{
+    *n = (int)(sizeof(kTypes) / sizeof(kTypes[0]));
+    return kTypes;
+}
+
 int type_size(MPI_Datatype dt)
 {
     if (const TypeInfo* t = type_info(dt)) return t->size;

@@ -65,6 +65,8 @@ struct TypeInfo {
 
 // Returns nullptr for handles that are not predefined reducible types.
 const TypeInfo* type_info(MPI_Datatype dt);
+// Every row type_info() can return (*n rows), for checks that walk the table.
+const TypeInfo* type_table(int* n);
 // Size in bytes of a predefined datatype (any predefined, including
 // non-reducible ones such as MPI_WCHAR); -1 if unknown.
 int type_size(MPI_Datatype dt);

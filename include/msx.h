@@ -19,6 +19,10 @@
  *   msx_unpack_dev           committed datatype (src/mpi/msmpi/mpid/segment.cpp,
  *                            called by MPI_Pack/MPI_Unpack, api/mpi_pack.cpp:41-660);
  *                            64-bit count, stream-ordered, device pointers.
+ *   msx_accumulate_dev    <- MPID_Uop_call(origin, target) over a derived target
+ *                            (win.cpp:1435, packethandling.cpp:2969-3004) and
+ *                            the two-datatype MPIR_Localcopy (mpid/pt2pt.cpp:
+ *                            770-948), with a type map on BOTH sides.
  *   msx_reduce_tree_dev   <- the per-step MPID_Uop_call chain of the
  *                            recursive-halving/doubling schedules
  *                            (src/mpi/msmpi/mpid/reduce.cpp:3899-3989,
@@ -294,6 +298,73 @@ int msx_pack_dev(const void* typed, int64_t count, MPI_Datatype datatype, void* 
                  void* stream);
 int msx_unpack_dev(const void* packed, int64_t count, MPI_Datatype datatype, void* typed,
                    void* stream);
+
+/* A combine between two datatype layouts: MPI_Accumulate's origin and target
+ * triples on device pointers, with no window.  Stream-ordered on `stream`; the
+ * call returns after the enqueue, allocates nothing and never synchronises
+ * (only the first GPU use of a type with an irregular type map uploads its run
+ * table, once, as with msx_pack_dev).
+ *
+ * The value.  Let n be the number of basic elements of origin_count instances
+ * of origin_type.  Element e of the origin is the e-th element of its type map
+ * in type-map order, instances `extent` apart; the same holds for the target.
+ * For e < n:
+ *     target[e] = origin[e] (op) target[e]
+ * the origin in the `in` role and the target in the `inout` role: the
+ * reference's MPID_Uop_call(origin, target) of an accumulate (win.cpp:1435).
+ * Equivalently, once the stream has drained the target holds the bytes of
+ *     msx_pack_dev(origin), msx_pack_dev(target),
+ *     msx_reduce_local_dev(in = packed origin, inout = the first n packed
+ *     target elements), msx_unpack_dev
+ * and no other byte of device memory is written.  MPI_REPLACE copies bytes
+ * (the typed -> typed MPIR_Localcopy) and accepts any two committed types,
+ * mixed structs included; MPI_NO_OP does nothing.  The origin may hold fewer
+ * data bytes than the target (MPI's rule): the last target instance is then
+ * partly covered.  The spans of the two operands may overlap (two columns of
+ * one matrix); the result is defined when no target-mapped byte among the n
+ * elements is an origin-mapped byte and the target map names no location
+ * twice.
+ *
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure:
+ *   1. either count negative: MPI_ERR_COUNT;
+ *   2. an invalid or uncommitted datatype: MPI_ERR_TYPE;
+ *   3. an invalid op handle, a user op (host or device) or MSX_SUM_WIDE:
+ *      MPI_ERR_OP;
+ *   4. more origin data bytes than target data bytes: MPI_ERR_TRUNCATE (data
+ *      bytes beyond 2^62 on either side: MPI_ERR_COUNT);
+ *   5. zero origin data bytes, or MPI_NO_OP: success, the pointers are never
+ *      looked at;
+ *   6. for any op except MPI_REPLACE the two types must share one basic
+ *      element type: a type with none (a mixed struct, the pair types
+ *      MPI_FLOAT_INT .. MPI_LONG_DOUBLE_INT) or two element types of different
+ *      kinds: MPI_ERR_TYPE; an (op, element type) pair outside the op's table:
+ *      MPI_ERR_OP; a type map that splits an element: MPI_ERR_TYPE;
+ *   7. a null origin or target: MPI_ERR_BUFFER;
+ *   8. no GPU: MPI_ERR_OTHER.
+ *
+ * msx_accumulate_plan runs checks 1 - 6 and reports what the call would do,
+ * without ever initialising a GPU (a pure function of its arguments; the call
+ * itself dispatches on the same plan).  *elements: n.  *granule: the bytes one
+ * work item moves when both bases are 16-byte aligned: the element size for an
+ * op, for MPI_REPLACE the largest power of two <= 16 dividing every run offset
+ * and length, the size and the extent of both layouts (0 with *path 0).
+ * *path:
+ *   0  nothing to do;
+ *   1  both sides contiguous: msx_reduce_local_dev's kernel (the engine's copy
+ *      kernel for MPI_REPLACE) on the two pieces;
+ *   2  the origin contiguous and covering whole target instances: the
+ *      derived-target accumulate of the one-sided path (msx_unpack_dev's
+ *      kernel for MPI_REPLACE);
+ *   3  MPI_REPLACE into a contiguous target: msx_pack_dev's kernel;
+ *   4  the two-layout kernel: one launch that maps element e on both sides.
+ * A null output pointer is MPI_ERR_ARG. */
+int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
+                       void* target, int64_t target_count, MPI_Datatype target_type,
+                       MPI_Op op, void* stream);
+int msx_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type,
+                        int64_t target_count, MPI_Datatype target_type, MPI_Op op,
+                        int64_t* elements, int* path, int* granule);
 
 /* out[i] = tree(srcs[0][i], ..., srcs[p-1][i]) with the balanced binary tree
  * ((s0 op s1) op (s2 op s3)) op ((s4 op s5) op (s6 op s7)), the left operand

@@ -21,6 +21,7 @@
 #include <memory>
 
 #include "msx_comm.h"
+#include "msx_kernels.h"
 #include "msx_runtime.h"
 
 namespace msx {
@@ -29,6 +30,11 @@ hipError_t launch_dt_copy(const DevLayout& L, int64_t count, void* typed, void* 
                           hipStream_t s);
 hipError_t launch_dt_acc(int opidx, Kind k, const DevLayout& L, int64_t count, const void* packed,
                          void* typed, hipStream_t s);
+// msx_acc2.hip
+hipError_t launch_dt_acc2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
+                          void* target, int64_t n, int align, hipStream_t s);
+hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target,
+                           int64_t bytes, int G, hipStream_t s);
 
 namespace {
 
@@ -925,6 +931,23 @@ int dtype_free(MPI_Datatype* h)
 // ---------------------------------------------------------------------------
 namespace {
 
+// DevLayout::align of a type, from the host form alone (no device layout needed).
+int layout_align(const Dtype* t)
+{
+    int64_t al = 16;
+    al = std::min(al, lowbit_align(t->size));
+    al = std::min(al, lowbit_align(t->extent));
+    if (t->rn) {
+        al = std::min({al, lowbit_align(t->rfirst), lowbit_align(t->rlen), lowbit_align(t->rstride)});
+        if (t->rn2 > 1) al = std::min(al, lowbit_align(t->rstride2));
+    }
+    for (const DtRun& r : t->runs) {
+        al = std::min(al, lowbit_align(r.disp));
+        al = std::min(al, lowbit_align(r.len));
+    }
+    return (int)al;
+}
+
 int build_dev_layout(Dtype* t)
 {
     if (t->dev_ready) return MPI_SUCCESS;
@@ -932,14 +955,9 @@ int build_dev_layout(Dtype* t)
     L.size = t->size;
     L.extent = t->extent;
     L.nruns = dtype_nruns(t);
-    int64_t al = 16;
-    al = std::min(al, lowbit_align(t->size));
-    al = std::min(al, lowbit_align(t->extent));
+    L.align = layout_align(t);
     if (t->rn) {
         // compact regular form: no run table at all
-        al = std::min({al, lowbit_align(t->rfirst), lowbit_align(t->rlen), lowbit_align(t->rstride)});
-        if (t->rn2 > 1) al = std::min(al, lowbit_align(t->rstride2));
-        L.align = (int)al;
         L.regular = 1;
         L.first = t->rfirst;
         L.blen = t->rlen;
@@ -952,11 +970,6 @@ int build_dev_layout(Dtype* t)
         t->dev_ready = true;
         return MPI_SUCCESS;
     }
-    for (const DtRun& r : t->runs) {
-        al = std::min(al, lowbit_align(r.disp));
-        al = std::min(al, lowbit_align(r.len));
-    }
-    L.align = (int)al;
     const size_t n = t->runs.size();
     bool regular = n >= 1;
     const int64_t stride0 = n > 1 ? t->runs[1].disp - t->runs[0].disp : 0;
@@ -1183,6 +1196,126 @@ int dt_acc_dev(int opidx, const Dtype* tc, int64_t count, const void* packed, vo
     L.align = (int)std::min<int64_t>({(int64_t)L.align, ptr_align(typed), ptr_align(packed)});
     hipError_t e = launch_dt_acc(opidx, ti->kind, L, count, packed, typed, s);
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "datatype accumulate");
+}
+
+namespace {
+
+// Every run of `t` holds whole elements of `esz` bytes (true for any type built
+// from one basic type whose data bytes are its extent).
+bool runs_hold_elements(const Dtype* t, int64_t esz)
+{
+    if (t->rn && t->rlen % esz) return false;
+    for (const DtRun& r : t->runs)
+        if (r.len % esz) return false;
+    return true;
+}
+
+// The first `bytes` (> 0) data bytes of the type's instances lie in one piece
+// at *disp: inside the first run, or over one-run instances that touch.
+bool contiguous_prefix(const Dtype* t, int64_t bytes, int64_t* disp)
+{
+    const DtRun first = t->rn ? DtRun{t->rfirst, t->rlen} : t->runs[0];
+    DtRun r{0, 0};
+    *disp = first.disp;
+    return bytes <= first.len || (single_run(t, &r) && t->size == t->extent);
+}
+
+}  // namespace
+
+// Checks 4 - 6 of msx_accumulate_dev (msx.h) and the path the call takes: a pure
+// function of the two host-side types, the counts and the op.
+int dt_acc2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, int64_t tcount, Acc2Plan* p)
+{
+    *p = Acc2Plan();
+    const int64_t lim = (int64_t)1 << 62;
+    if ((ot->size > 0 && ocount > lim / ot->size) || (tt->size > 0 && tcount > lim / tt->size)) {
+        set_error("count overflows the data size");
+        return MPI_ERR_COUNT;
+    }
+    const int64_t obytes = ocount * ot->size, tbytes = tcount * tt->size;
+    if (obytes > tbytes) {
+        set_error("accumulate truncated: %lld origin bytes into %lld", (long long)obytes, (long long)tbytes);
+        return MPI_ERR_TRUNCATE;
+    }
+    // n_elements also counts the MPI_LB / MPI_UB markers of a struct (a subarray has two)
+    p->elements = ot->el_size > 0 ? obytes / ot->el_size : ocount * ot->n_elements;
+    p->bytes = obytes;
+    if (obytes == 0 || opidx == O_NOOP) return MPI_SUCCESS;
+    if (opidx == O_REPLACE) {
+        p->granule = std::min(layout_align(ot), layout_align(tt));
+    } else {
+        const TypeInfo* oi = type_info(ot->eltype);
+        const TypeInfo* ti = type_info(tt->eltype);
+        if (ot->eltype == MPI_DATATYPE_NULL || tt->eltype == MPI_DATATYPE_NULL) {
+            set_error("%s datatype has no single basic element type", ot->eltype == MPI_DATATYPE_NULL ? "origin" : "target");
+            return MPI_ERR_TYPE;
+        }
+        if ((oi ? oi->kind : K_NONE) != (ti ? ti->kind : K_NONE)) {
+            set_error("origin elements 0x%x and target elements 0x%x differ in kind", ot->eltype, tt->eltype);
+            return MPI_ERR_TYPE;
+        }
+        for (MPI_Datatype el : {ot->eltype, tt->eltype})
+            if (!type_info(el) || op_check_dtype(opidx, el) != MPI_SUCCESS) {
+                set_error("%s is not defined for datatype 0x%x", op_name(opidx), el);
+                return MPI_ERR_OP;
+            }
+        if (!runs_hold_elements(ot, oi->size) || !runs_hold_elements(tt, ti->size)) {
+            set_error("datatype runs split elements of 0x%x", tt->eltype);
+            return MPI_ERR_TYPE;
+        }
+        p->granule = ti->size;
+    }
+    int64_t od, td;
+    const bool oc = contiguous_prefix(ot, obytes, &od), tc = contiguous_prefix(tt, obytes, &td);
+    if (oc && tc) p->path = 1;
+    else if (oc && obytes % tt->size == 0) p->path = 2;      // dt_acc_dev covers whole target instances
+    else if (tc && opidx == O_REPLACE) p->path = 3;
+    else p->path = 4;
+    return MPI_SUCCESS;
+}
+
+int dt_acc2_dev(int opidx, const Dtype* otc, int64_t ocount, const void* origin, const Dtype* ttc, void* target,
+                const Acc2Plan& p, hipStream_t s)
+{
+    if (p.path == 0) return MPI_SUCCESS;
+    int64_t od = 0, td = 0;
+    (void)contiguous_prefix(otc, p.bytes, &od);
+    (void)contiguous_prefix(ttc, p.bytes, &td);
+    const char* src = static_cast<const char*>(origin) + od;      // paths 1, 2: the origin's one piece
+    char* dst = static_cast<char*>(target) + td;                  // paths 1, 3: the target's
+    const TypeInfo* ti = type_info(ttc->eltype);                  // an op's element (checked by the plan)
+    switch (p.path) {
+    case 1: {
+        if (opidx != O_REPLACE) return reduce_local_device(opidx, ti->kind, src, dst, (size_t)(p.bytes / ti->size), s);
+        const void* ps = src;
+        void* pd = dst;
+        const size_t nb = (size_t)p.bytes;
+        const hipError_t e = launch_copy_segs(&ps, &pd, &nb, 1, s);
+        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "copy kernel launch");
+    }
+    case 2:
+        return dt_acc_dev(opidx, ttc, p.bytes / ttc->size, src, target, s);
+    case 3:
+        return dt_pack_dev(otc, ocount, origin, dst, s);
+    default:
+        break;
+    }
+    Dtype* ot = const_cast<Dtype*>(otc);
+    Dtype* tt = const_cast<Dtype*>(ttc);
+    int rc;
+    {
+        std::lock_guard<std::recursive_mutex> g(g_mu);
+        rc = build_dev_layout(ot);
+        if (rc == MPI_SUCCESS) rc = build_dev_layout(tt);
+    }
+    if (rc != MPI_SUCCESS) return rc;
+    const int align = (int)std::min<int64_t>({(int64_t)ot->dev.align, (int64_t)tt->dev.align, ptr_align(origin),
+                                              ptr_align(target)});
+    const hipError_t e = opidx == O_REPLACE
+                             ? launch_dt_copy2(ot->dev, origin, tt->dev, target, p.bytes, align, s)
+                             : launch_dt_acc2(opidx, ti->kind, ot->dev, origin, tt->dev, target, p.bytes / ti->size,
+                                              align, s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout datatype accumulate");
 }
 
 int dt_pack_any(const Dtype* t, int64_t count, const void* typed, void* packed)

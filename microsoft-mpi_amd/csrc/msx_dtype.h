@@ -131,6 +131,23 @@ int dt_unpack_dev(const Dtype* t, int64_t count, const void* packed, void* typed
 // pair outside the op's table, leaves `typed` unchanged (op_errno only).
 int dt_acc_dev(int opidx, const Dtype* t, int64_t count, const void* packed, void* typed, hipStream_t s);
 
+// msx_accumulate_dev (msx.h): target elem e = origin elem e (op) target elem e
+// over TWO type maps, e below the origin's element count.  dt_acc2_plan runs the
+// call's checks 4 - 6 on the host-side types (no GPU is touched) and says what
+// the call does; dt_acc2_dev does exactly that: paths 1 - 3 forward to the
+// contiguous combine / copy, dt_acc_dev / dt_unpack_dev and dt_pack_dev, path 4
+// is the two-layout kernel of msx_acc2.hip.
+struct Acc2Plan {
+    int64_t elements = 0;   // basic elements of the origin
+    int64_t bytes = 0;      // data bytes of the origin
+    int path = 0;           // 0 nothing to do, 1 - 4 as in msx.h
+    int granule = 0;        // bytes one work item moves (16-byte aligned bases)
+};
+int dt_acc2_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const Dtype* target_t,
+                 int64_t target_count, Acc2Plan* plan);
+int dt_acc2_dev(int opidx, const Dtype* origin_t, int64_t origin_count, const void* origin,
+                const Dtype* target_t, void* target, const Acc2Plan& plan, hipStream_t s);
+
 // Blocking forms that accept host (pageable or pinned) or device buffers.
 int dt_pack_any(const Dtype* t, int64_t count, const void* typed, void* packed);
 int dt_unpack_any(const Dtype* t, int64_t count, const void* packed, void* typed);

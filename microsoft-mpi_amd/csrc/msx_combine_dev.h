@@ -36,12 +36,63 @@ __device__ __forceinline__ size_t combine_tile(unsigned b, unsigned nb)
     }
 }
 
+// Cache policy of the body's three 16-byte streams.  `in` is never read again,
+// the `inout` read is overwritten at once, the `inout` write is what the next
+// combine on the same operands re-reads.  plain / nt are the global accesses
+// of ld<> / st<>; the scope-bit forms (sc1: bypasses L1 on a load, drops the
+// line from the XCD's L2 on a store) are raw buffer accesses.
+enum class LdPol { plain, nt, sc1, sc1_nt };
+enum class StPol { plain, nt, sc1, sc0_sc1 };
+template <LdPol IN, LdPol IO, StPol ST>
+struct CombinePolicy {
+    static constexpr LdPol in = IN, io = IO;
+    static constexpr StPol st = ST;
+};
+// What the two flags of the launchers have always meant.
+template <bool NTLD, bool NTST>
+using FlagPolicy = CombinePolicy<NTLD ? LdPol::nt : LdPol::plain, NTLD ? LdPol::nt : LdPol::plain,
+                                 NTST ? StPol::nt : StPol::plain>;
+
+// Buffer offsets are 32-bit: the resource is rebased on each tile (`tile`,
+// workgroup-uniform, so it stays in scalar registers) and `off` is the lane's
+// byte offset inside the tile, so operands of any size work.  `p` is the same
+// address as a pointer, for the global forms.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const u32x4* tile)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(tile), 0, (int)0xFFFFFFFF, 0x00020000);
+}
+template <LdPol P>
+__device__ __forceinline__ u32x4 ld_pol(const u32x4* p, const u32x4* tile, unsigned off)
+{
+    if constexpr (P == LdPol::plain) return ld<false>(p);
+    else if constexpr (P == LdPol::nt) return ld<true>(p);
+    else if constexpr (P == LdPol::sc1) return __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(tile), (int)off, 0, 16);
+    else return __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(tile), (int)off, 0, 18);     // sc1 nt
+}
+template <StPol P>
+__device__ __forceinline__ void st_pol(u32x4* p, u32x4* tile, unsigned off, u32x4 v)
+{
+    if constexpr (P == StPol::plain) st<false>(p, v);
+    else if constexpr (P == StPol::nt) {
+        // The value goes through an empty asm first: stored straight out of
+        // apply_vec, the optimiser drops the store's non-temporal mark and
+        // emits a plain global_store_dwordx4.
+        asm volatile("" : "+v"(v));
+        st<true>(p, v);
+    }
+    else if constexpr (P == StPol::sc1) __builtin_amdgcn_raw_buffer_store_b128(v, tile_rsrc(tile), (int)off, 0, 16);
+    else __builtin_amdgcn_raw_buffer_store_b128(v, tile_rsrc(tile), (int)off, 0, 17);        // sc0 sc1
+}
+
 // Elements [0, head) and [head + nvec*EPV, head + nvec*EPV + tail) are scalar;
 // the vector body starts at element `head`, 16-byte aligned for both operands.
 // T  = element type used for scalar elements;
 // VT = lane type used inside a 16-byte vector (== T except bitwise ops, which
 //      run on 32-bit words regardless of the MPI element type).
-template <int OP, class T, class VT, int UNROLL, int BLOCK, bool NTLD, bool NTST, int XG = 0>
+// POL = cache policy of the full tiles' vector accesses; partial tiles and
+//      scalar elements keep plain accesses.
+template <int OP, class T, class VT, int UNROLL, int BLOCK, bool NTLD, bool NTST, int XG = 0,
+          class POL = FlagPolicy<NTLD, NTST>>
 __device__ __forceinline__ void combine_body(const T* __restrict__ in, T* __restrict__ io, size_t head,
                                              size_t nvec, size_t tail)
 {
@@ -55,10 +106,11 @@ __device__ __forceinline__ void combine_body(const T* __restrict__ in, T* __rest
         const size_t i0 = t0 + threadIdx.x;
         if (t0 + TILE <= nvec) {
             u32x4 a[UNROLL], b[UNROLL];
+            const unsigned off0 = threadIdx.x * 16u;
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
-                a[u] = ld<NTLD>(vin + i0 + (size_t)u * BLOCK);
-                b[u] = ld<NTLD>(vio + i0 + (size_t)u * BLOCK);
+                a[u] = ld_pol<POL::in>(vin + i0 + (size_t)u * BLOCK, vin + t0, off0 + (unsigned)u * BLOCK * 16u);
+                b[u] = ld_pol<POL::io>(vio + i0 + (size_t)u * BLOCK, vio + t0, off0 + (unsigned)u * BLOCK * 16u);
             }
             // Every load of the tile is issued before the first use: without
             // this the compiler hoists work on the first operand (logical ops,
@@ -68,7 +120,8 @@ __device__ __forceinline__ void combine_body(const T* __restrict__ in, T* __rest
             for (int u = 0; u < UNROLL; ++u) issued_together(a[u], b[u]);
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
-                st<NTST>(vio + i0 + (size_t)u * BLOCK, apply_vec<OP, VT>(b[u], a[u]));
+                st_pol<POL::st>(vio + i0 + (size_t)u * BLOCK, vio + t0, off0 + (unsigned)u * BLOCK * 16u,
+                                apply_vec<OP, VT>(b[u], a[u]));
         } else {
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
@@ -91,6 +144,21 @@ __device__ __forceinline__ void combine_body(const T* __restrict__ in, T* __rest
             io[e] = Fn<OP>::apply(io[e], in[e]);
         }
     }
+}
+
+// The product's DRAM-regime body (k_combine_dram, and the probe library's
+// default_body_probe): UNROLL 1, XCD runs of kDramRun tiles, the launcher's
+// load policy, and sc1 (write-through) stores whatever NTST says: the XCD's L2
+// does not keep the written line, which nothing re-reads before a pass over
+// all of both operands has gone through that L2 (table at k_combine_dram).
+constexpr int kDramRun = 128;
+template <bool NTLD>
+using DramPolicy = CombinePolicy<NTLD ? LdPol::nt : LdPol::plain, NTLD ? LdPol::nt : LdPol::plain, StPol::sc1>;
+template <int OP, class T, class VT, int BLOCK, bool NTLD, bool NTST>
+__device__ __forceinline__ void combine_dram_body(const T* __restrict__ in, T* __restrict__ io, size_t head,
+                                                  size_t nvec, size_t tail)
+{
+    combine_body<OP, T, VT, 1, BLOCK, NTLD, NTST, kDramRun, DramPolicy<NTLD>>(in, io, head, nvec, tail);
 }
 
 // Operand split of the vector body: head scalars up to 16-byte alignment,

@@ -46,12 +46,27 @@ __global__ __launch_bounds__(BLOCK) void k_combine(const T* __restrict__ in, T* 
 // 113.4 / 137.2 -> 130.3, 512 MiB 280.9 -> 264.5 / 274.2 -> 262.2, 2 GiB
 // 1096 -> 1061 / 1093 -> 1059; 1 GiB within 0.5 %.  Runs of 64, 256 and 512
 // tiles, 128-lane workgroups and XCD-contiguous eighths do not beat it.
-constexpr int kDramRun = 128;
+//
+// Cache policy (combine_dram_body): non-temporal loads of both operands, sc1
+// stores.  Picked from the probe library's matrix of 4 `in` loads x 2 `inout`
+// loads x 4 stores (bench.py --sweep, fresh process per column, median of 3
+// rounds x 10 launches, us; "plain" = the plain store every round before had;
+// the same body under two symbols differed by 0.0-0.1 us up to 256 MiB and by
+// at most 1.3 us above; profiles/r07/sweep/):
+//   MiB per operand   24    32    64   128   192   256 (2 processes)  384   512   1024   2048
+//   nt, nt, plain   11.2  15.1  31.4  58.9  87.0  114.5 / 112.8     203.0 276.5  556.0 1101.8
+//   nt, nt, sc1     10.2  13.8  29.0  55.6  81.9  109.5 / 109.7     192.6 260.2  516.3 1045.3
+// 2.7-9 % at every size, and the spread between processes at 256 MiB goes
+// (109.4-109.7 us where plain stores gave 112.8-114.5).  sc0 sc1 stores and
+// sc1 on the loads measure the same as this; a store that really carries nt
+// (the non-temporal store of earlier sweeps compiled to a plain one) loses
+// 5 % up to 256 MiB and wins 7-9 % above; plain loads of `in` lose 9-21 % at
+// 256 MiB.  So one policy for the whole regime, no size bound.
 template <int OP, class T, class VT, int BLOCK, bool NTLD, bool NTST>
 __global__ __launch_bounds__(BLOCK) void k_combine_dram(const T* __restrict__ in, T* __restrict__ io,
                                                         size_t head, size_t nvec, size_t tail)
 {
-    combine_body<OP, T, VT, 1, BLOCK, NTLD, NTST, kDramRun>(in, io, head, nvec, tail);
+    combine_dram_body<OP, T, VT, BLOCK, NTLD, NTST>(in, io, head, nvec, tail);
 }
 
 // Same body, launched by the host-memory path of MPI_Reduce_local (pinned
@@ -335,7 +350,10 @@ hipError_t run_combine(const void* in, void* io, size_t count, hipStream_t s, co
 // 256-thread workgroups (one-shot grid, 65536 workgroups at 256 MiB fp32),
 // non-temporal loads.  Measured on MI355X for the 256 MiB fp32 SUM
 // (profiles/r01/bench_sweep.log): 7.05 TB/s vs 6.8 TB/s at 4 vectors per lane
-// and 5.5 TB/s with default-policy loads.
+// and 5.5 TB/s with default-policy loads.  The store flag (plain) holds up to
+// combine_dram_min and for host operands; above, k_combine_dram stores sc1
+// whatever the flag says (combine_dram_body): 256 MiB fp32 SUM 112.5-116.8 ->
+// 109.3-110.7 us, 7.28-7.37 TB/s (profiles/r07/).
 template <int OP, class T>
 hipError_t run_default(const void* in, void* io, size_t count, hipStream_t s, const LaunchCfg& cfg)
 {

@@ -1,6 +1,7 @@
 """msx.probe — ctypes binding of libmsx_probe.so, the bench-only measurement
 kernels (microsoft-mpi_amd/probe/msx_probe.hip): HBM stream-mix probes and the
-fp32 SUM combine body in other launch geometries.  Used by bench.py, the
+fp32 SUM combine body in other launch geometries and with other cache policies
+per stream (in_<in load>_io_<inout load>_st_<inout store>).  Used by bench.py, the
 scripts and the GPU tests that check the variants compute the same bits; the
 product library libmsmpi_mi355x.so neither contains nor loads any of it.
 """

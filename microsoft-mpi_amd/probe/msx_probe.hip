@@ -11,7 +11,8 @@
 //     device code of k_combine / k_combine_dram) in other launch geometries,
 //     for the tuning sweep, and the default DRAM-regime body under its own
 //     symbol (k_probe_combine<..., 64, ..., -1>) so single cold-cache launches
-//     stay out of the headline kernel's rocprof statistics;
+//     stay out of the headline kernel's rocprof statistics, and the same
+//     geometry with every cache policy per stream (k_probe_combine_pol);
 //   * msxp_tree8: the product's 8-source DRAM-regime tree (k_tree, fp32 SUM,
 //     non-temporal loads, one-wave workgroups) in another tile order.
 #include <hip/hip_runtime.h>
@@ -73,6 +74,26 @@ __global__ __launch_bounds__(BLOCK) void k_probe_combine(const float* __restrict
     combine_body<O_SUM, float, float, UNROLL, BLOCK, NTLD, NTST, XG>(in, io, head, nvec, tail);
 }
 
+// default_body_probe: exactly what k_combine_dram<3, float, float, 64, true,
+// false> runs (combine_dram_body, its cache policy included), under this symbol
+template <>
+__global__ __launch_bounds__(64) void k_probe_combine<1, 64, true, false, kDramRun>(const float* __restrict__ in,
+                                                                                    float* __restrict__ io,
+                                                                                    size_t head, size_t nvec,
+                                                                                    size_t tail)
+{
+    combine_dram_body<O_SUM, float, float, 64, true, false>(in, io, head, nvec, tail);
+}
+
+// The DRAM-regime body (one-wave workgroups, XCD runs of 128 tiles) with a
+// cache policy per stream: `in` load, `inout` load, `inout` store.
+template <LdPol IN, LdPol IO, StPol ST>
+__global__ __launch_bounds__(64) void k_probe_combine_pol(const float* __restrict__ in, float* __restrict__ io,
+                                                          size_t head, size_t nvec, size_t tail)
+{
+    combine_body<O_SUM, float, float, 1, 64, true, false, kDramRun, CombinePolicy<IN, IO, ST>>(in, io, head, nvec, tail);
+}
+
 // the "LDS staging of the incoming chunk" form: `in` goes global -> LDS ->
 // registers.  Each element is used once, so the stage only adds an LDS write
 // + read per byte and a barrier (measured, not asserted)
@@ -114,6 +135,21 @@ hipError_t run_variant(const void* in, void* io, size_t count, hipStream_t s)
     if (grid == 0) return hipSuccess;
     if (grid > 0x7fffffffu) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_probe_combine<UNROLL, BLOCK, NTLD, NTST, XG>), dim3((unsigned)grid), dim3(BLOCK), 0, s,
+                       static_cast<const float*>(in), static_cast<float*>(io), head, nvec, tail);
+    return hipGetLastError();
+}
+
+template <LdPol IN, LdPol IO, StPol ST>
+hipError_t run_variant_pol(const void* in, void* io, size_t count, hipStream_t s)
+{
+    size_t head, nvec, tail;
+    combine_split<float>(in, io, count, head, nvec, tail);
+    size_t grid = (nvec + 63) / 64;
+    const size_t sc = (head + tail + 63) / 64;
+    if (grid < sc) grid = sc;
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_probe_combine_pol<IN, IO, ST>), dim3((unsigned)grid), dim3(64), 0, s,
                        static_cast<const float*>(in), static_cast<float*>(io), head, nvec, tail);
     return hipGetLastError();
 }
@@ -163,6 +199,18 @@ const Variant kVariants[] = {
     {"u1_b128_ntld_xg128", run_variant<1, 128, true, false, 128>},
     {"u1_b64_ntall_xg128", run_variant<1, 64, true, true, 128>},
     {"u1_b256_lds", run_variant_lds<256>},
+    // the default geometry with each stream's cache policy chosen on its own:
+    // in_<`in` load>_io_<`inout` load>_st_<`inout` store>; in_nt_io_nt_st_sc1
+    // is the default body's policy, in_nt_io_nt_st_plain what it was before
+#define MSXP_POL_ST(I, IN, O, IO)                                                             \
+    {"in_" #I "_io_" #O "_st_plain", run_variant_pol<LdPol::IN, LdPol::IO, StPol::plain>},    \
+    {"in_" #I "_io_" #O "_st_nt", run_variant_pol<LdPol::IN, LdPol::IO, StPol::nt>},          \
+    {"in_" #I "_io_" #O "_st_sc1", run_variant_pol<LdPol::IN, LdPol::IO, StPol::sc1>},        \
+    {"in_" #I "_io_" #O "_st_sc0sc1", run_variant_pol<LdPol::IN, LdPol::IO, StPol::sc0_sc1>},
+#define MSXP_POL_IO(I, IN) MSXP_POL_ST(I, IN, plain, plain) MSXP_POL_ST(I, IN, nt, nt)
+    MSXP_POL_IO(plain, plain) MSXP_POL_IO(nt, nt) MSXP_POL_IO(sc1, sc1) MSXP_POL_IO(sc1nt, sc1_nt)
+#undef MSXP_POL_IO
+#undef MSXP_POL_ST
 };
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 

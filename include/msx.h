@@ -23,6 +23,11 @@
  *                            (win.cpp:1435, packethandling.cpp:2969-3004) and
  *                            the two-datatype MPIR_Localcopy (mpid/pt2pt.cpp:
  *                            770-948), with a type map on BOTH sides.
+ *   msx_fetch_and_op_dev /<- the target side of MPI_Fetch_and_op /
+ *   msx_get_accumulate_dev   MPI_Get_accumulate (win.cpp:1804,
+ *                            Handle_MPIDI_CH3_PKT_GET_ACCUMULATE,
+ *                            packethandling.cpp:2121): the old target value
+ *                            into the result, then MPID_Uop_call(origin, target).
  *   msx_reduce_tree_dev   <- the per-step MPID_Uop_call chain of the
  *                            recursive-halving/doubling schedules
  *                            (src/mpi/msmpi/mpid/reduce.cpp:3899-3989,
@@ -365,6 +370,106 @@ int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype or
 int msx_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type,
                         int64_t target_count, MPI_Datatype target_type, MPI_Op op,
                         int64_t* elements, int* path, int* granule);
+
+/* The combine that also hands back the old value, in ONE launch:
+ * MPI_Fetch_and_op's value on device pointers, with no window.  For i < count:
+ *     fetched[i] = inout[i]              (the old bytes, copied whole, the
+ *                                         padding of a pair struct included)
+ *     inout[i]   = inout[i] (op) in[i]
+ * Stream-ordered on `stream`; returns after the enqueue, allocates nothing and
+ * never synchronises.  Once the stream has drained, inout holds exactly the
+ * bytes msx_reduce_local_dev(in, inout, count, datatype, op, stream) would have
+ * produced and fetched the bytes inout had before; no other byte of device
+ * memory is written.  The call moves 4 N bytes where msx_copy_dev +
+ * msx_reduce_local_dev move 5 N in two launches.
+ * Ops: every (builtin op, predefined datatype) pair msx_reduce_local_dev
+ * accepts, MSX_FLOAT16 / MSX_BFLOAT16 and the pair types under MPI_MAXLOC /
+ * MPI_MINLOC included; MSX_SUM_WIDE is MPI_SUM's combine; MPI_REPLACE
+ * (inout[i] = in[i]) and MPI_NO_OP (inout unchanged; `in` is never looked at
+ * and may be NULL) on any predefined datatype with data bytes.  User ops, host
+ * or device, are MPI_ERR_OP.
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure:
+ *   1. count == 0: success;
+ *   2. an invalid op handle, a user op or an illegal (op, datatype) pair:
+ *      MPI_ERR_OP;
+ *   3. a negative count: MPI_ERR_COUNT;
+ *   4. a null inout or fetched, or a null in unless the op is MPI_NO_OP:
+ *      MPI_ERR_BUFFER;
+ *   5. in == inout: MPI_ERR_BUFFER;
+ *   6. the byte range of fetched meeting the range of inout or of in:
+ *      MPI_ERR_BUFFER, and msx_last_error() names the two operands;
+ *   7. no GPU: MPI_ERR_OTHER.
+ * The 16-byte vector body runs when in, fetched and inout share one offset
+ * from 16-byte alignment (with head and tail elements in the same launch);
+ * any other placement runs the whole call element by element.  There is no
+ * realigning form as msx_reduce_local_dev has for two operands. */
+int msx_fetch_and_op_dev(const void* in, void* fetched, void* inout, int64_t count,
+                         MPI_Datatype datatype, MPI_Op op, void* stream);
+
+/* Fetch and combine between three datatype layouts: MPI_Get_accumulate's
+ * origin, result and target triples on device pointers, with no window.
+ * Stream-ordered on `stream`; returns after the enqueue, allocates nothing and
+ * never synchronises (only the first GPU use of a type with an irregular type
+ * map uploads its run table, once, as with msx_pack_dev).
+ *
+ * The value.  Element e of a triple is defined as in msx_accumulate_dev.  Let
+ * n be the number of basic elements of the origin triple; under MPI_NO_OP, of
+ * the RESULT triple, and the origin triple (pointer, count and datatype) is
+ * ignored entirely.  For e < n:
+ *     result[e] = target[e]                 (the old value)
+ *     target[e] = origin[e] (op) target[e]
+ * the origin in the `in` role.  MPI_REPLACE: target[e] = origin[e], bytes, any
+ * committed types; MPI_NO_OP leaves the target unchanged (MPI_Get).  Once the
+ * stream has drained the target holds the bytes of msx_accumulate_dev(origin,
+ * target) and the result the bytes of msx_accumulate_dev(MPI_REPLACE, target ->
+ * result) taken before it; no other byte of device memory is written.  The
+ * result and the target may each hold more data than the n elements; the rest
+ * is untouched.  The spans may interleave; the call is defined when no
+ * result-mapped byte among the n elements is an origin- or target-mapped byte,
+ * no target-mapped byte is an origin-mapped byte, and neither the result map
+ * nor the target map names a location twice.
+ *
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure:
+ *   1. any count negative: MPI_ERR_COUNT;
+ *   2. an invalid or uncommitted datatype: MPI_ERR_TYPE (the origin's is not
+ *      checked under MPI_NO_OP);
+ *   3. an invalid op handle, a user op (host or device) or MSX_SUM_WIDE:
+ *      MPI_ERR_OP;
+ *   4. the n elements' data bytes exceeding the target's or the result's data
+ *      bytes: MPI_ERR_TRUNCATE (data bytes beyond 2^62: MPI_ERR_COUNT);
+ *   5. zero bytes to move: success, the pointers are never looked at;
+ *   6. for any op except MPI_REPLACE / MPI_NO_OP the three types must share one
+ *      basic element kind, legal for the op, and no type map may split an
+ *      element; the classes are msx_accumulate_dev's (MPI_ERR_TYPE, or
+ *      MPI_ERR_OP for an illegal (op, element type) pair);
+ *   7. a null result or target, or a null origin unless MPI_NO_OP:
+ *      MPI_ERR_BUFFER;
+ *   8. no GPU: MPI_ERR_OTHER.
+ *
+ * msx_get_accumulate_plan runs checks 1 - 6 and reports what the call would
+ * do, without ever initialising a GPU (a pure function of its arguments; the
+ * call itself dispatches on the same plan).  *elements: n.  *granule: the
+ * element size for an op; for MPI_REPLACE / MPI_NO_OP the largest power of two
+ * <= 16 dividing every run offset and length, the size and the extent of the
+ * layouts involved (0 with *path 0).  *path:
+ *   0  nothing to do;
+ *   1  all three pieces contiguous: msx_fetch_and_op_dev's kernel (the engine's
+ *      copy kernel for MPI_NO_OP);
+ *   2  MPI_NO_OP, not all contiguous: msx_accumulate_dev(MPI_REPLACE, target ->
+ *      result), with whatever path that plan takes (its two-layout kernel when
+ *      the n elements end inside a target instance);
+ *   3  the three-layout kernel: one launch that maps element e on all sides.
+ * A null output pointer is MPI_ERR_ARG. */
+int msx_get_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
+                           void* result, int64_t result_count, MPI_Datatype result_type,
+                           void* target, int64_t target_count, MPI_Datatype target_type,
+                           MPI_Op op, void* stream);
+int msx_get_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type,
+                            int64_t result_count, MPI_Datatype result_type,
+                            int64_t target_count, MPI_Datatype target_type, MPI_Op op,
+                            int64_t* elements, int* path, int* granule);
 
 /* out[i] = tree(srcs[0][i], ..., srcs[p-1][i]) with the balanced binary tree
  * ((s0 op s1) op (s2 op s3)) op ((s4 op s5) op (s6 op s7)), the left operand

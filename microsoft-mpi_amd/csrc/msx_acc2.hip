@@ -37,14 +37,6 @@
 namespace msx {
 namespace dev {
 
-// Byte offset of granule g in either kind of layout.
-template <int G, bool NARROW>
-__device__ __forceinline__ int64_t map_off(const CopyArgs& a, int64_t g)
-{
-    if (a.poff) return typed_off<G, false, NARROW>(a, g);      // uniform: a kernel argument
-    return typed_off<G, true, NARROW>(a, g);
-}
-
 // target element (op)= origin element; acc_elem's two forms (msx_pack.hip).
 template <int OP, class T, bool ALIGNED>
 __device__ __forceinline__ void acc2_elem(char* t, const char* o)

@@ -160,6 +160,61 @@ MSX_EXPORT int msx_reduce_local_dev(const void* in, void* inout, int64_t count, 
     return reduce_local_device(r.opidx, type_info(dt)->kind, in, inout, (size_t)count, s);
 }
 
+// ---- msx_fetch_and_op_dev: the combine that hands back the old inout ----------
+// msx_reduce_local_dev's checks in its order with `fetched` added (msx.h);
+// MPI_REPLACE and MPI_NO_OP are legal here as in MPI_Fetch_and_op, on any
+// predefined datatype.
+MSX_EXPORT int msx_fetch_and_op_dev(const void* in, void* fetched, void* inout, int64_t count, MPI_Datatype dt,
+                                    MPI_Op op, void* stream)
+{
+    if (count == 0) return MPI_SUCCESS;
+    OpRef r;
+    int rc = v_op_handle(op, &r);
+    if (rc != MPI_SUCCESS) return rc;
+    if (r.opidx == O_NULL) { set_error("msx_fetch_and_op_dev takes builtin ops only"); return MPI_ERR_OP; }
+    const bool moves_bytes = r.opidx == O_REPLACE || r.opidx == O_NOOP;
+    int esz;
+    if (moves_bytes) {
+        esz = type_size(dt);       // a pair type's whole struct, padding included
+        if (esz <= 0) {
+            set_error("MPI_Op 0x%x (%s) takes a predefined datatype with data, not 0x%x", op, op_name(r.opidx), dt);
+            return MPI_ERR_OP;
+        }
+    } else {
+        rc = op_check_dtype(r.opidx, dt);
+        if (rc != MPI_SUCCESS || !type_info(dt)) {
+            set_error("MPI_Op 0x%x (%s) is not defined for datatype 0x%x", op, op_name(r.opidx), dt);
+            return MPI_ERR_OP;
+        }
+        esz = type_info(dt)->size;
+    }
+    if (count < 0 || (uint64_t)count > (UINT64_MAX >> 2) / (uint64_t)esz) {
+        set_error("bad count (%lld)", (long long)count);
+        return MPI_ERR_COUNT;
+    }
+    const bool noop = r.opidx == O_NOOP;
+    if (!inout || !fetched || (!in && !noop)) { set_error("null buffer"); return MPI_ERR_BUFFER; }
+    if (!noop && in == inout) { set_error("inbuf aliases inoutbuf"); return MPI_ERR_BUFFER; }
+    const size_t nb = (size_t)count * (size_t)esz;
+    const uintptr_t f = (uintptr_t)fetched, io = (uintptr_t)inout, a = (uintptr_t)in;
+    if (f < io + nb && io < f + nb) { set_error("fetched overlaps inout"); return MPI_ERR_BUFFER; }
+    if (!noop && f < a + nb && a < f + nb) { set_error("fetched overlaps in"); return MPI_ERR_BUFFER; }
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the HIP null stream
+    hipError_t e;
+    if (noop) {
+        const void* ps = inout;
+        void* pd = fetched;
+        e = launch_copy_segs(&ps, &pd, &nb, 1, s);
+    } else if (r.opidx == O_REPLACE) {
+        e = launch_fetch_combine(O_REPLACE, K_U8, in, fetched, inout, nb, s);
+    } else {
+        e = launch_fetch_combine(r.opidx, type_info(dt)->kind, in, fetched, inout, (size_t)count, s);
+    }
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "fetch-and-combine kernel launch");
+}
+
 // ---- msx_reduce_local_batch_dev: many small combines in few launches ---------
 namespace {
 // Mutually misaligned segments (operands at different offsets from 16-byte

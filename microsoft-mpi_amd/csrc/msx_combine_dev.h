@@ -1,8 +1,9 @@
 // msx_combine_dev.h — the streaming combine body `inout[i] = op(inout[i], in[i])`
 // (src/mpi/msmpi/mpid/op.cpp:14-160 as an HBM stream).  Device code only;
-// included by msx_kernels.hip (the product kernels) and by the bench-only
-// probe library (probe/msx_probe.hip), which times the same body under other
-// symbols and in other tile orders.
+// included by msx_kernels.hip (the product kernels), by msx_fetch.hip (the
+// fetch form of the body, fetch_body below) and by the bench-only probe library
+// (probe/msx_probe.hip), which times the same bodies under other symbols, in
+// other tile orders and with other cache policies.
 #pragma once
 
 #include "msx_dev_ops.h"
@@ -161,6 +162,96 @@ __device__ __forceinline__ void combine_dram_body(const T* __restrict__ in, T* _
     combine_body<OP, T, VT, 1, BLOCK, NTLD, NTST, kDramRun, DramPolicy<NTLD>>(in, io, head, nvec, tail);
 }
 
+// ---- the fetch form (msx_fetch_and_op_dev, msx.h) ------------------------------
+//   fetched[i] = inout[i]   (the old bytes, whole: a pair struct's padding too)
+//   inout[i]   = inout[i] (op) in[i]
+// combine_body with one more store per vector: the loaded `inout` vector goes to
+// `fetched` as it came, then apply_vec's result to `inout`.  4 N bytes against
+// the 2 N copy + 3 N combine of the two calls it replaces.  OP may also be
+// O_REPLACE (inout[i] = in[i]), which has no functor: it moves bytes.
+template <int OP, class VT>
+__device__ __forceinline__ u32x4 fetch_apply_vec(u32x4 io, u32x4 in)
+{
+    if constexpr (OP == O_REPLACE) return in;
+    else return apply_vec<OP, VT>(io, in);
+}
+template <int OP, class T>
+__device__ __forceinline__ T fetch_apply(T io, T in)
+{
+    if constexpr (OP == O_REPLACE) return in;
+    else return Fn<OP>::apply(io, in);
+}
+
+// POL: the combine's policy of its three streams; FST: the `fetched` store's.
+// Partial tiles and scalar elements keep plain accesses, as in combine_body.
+template <int OP, class T, class VT, int UNROLL, int BLOCK, int XG, class POL, StPol FST>
+__device__ __forceinline__ void fetch_body(const T* __restrict__ in, T* __restrict__ io, T* __restrict__ fo,
+                                           size_t head, size_t nvec, size_t tail)
+{
+    constexpr size_t EPV = 16 / sizeof(T);
+    constexpr size_t TILE = (size_t)BLOCK * UNROLL;
+    const u32x4* __restrict__ vin = reinterpret_cast<const u32x4*>(in + head);
+    u32x4* __restrict__ vio = reinterpret_cast<u32x4*>(io + head);
+    u32x4* __restrict__ vfo = reinterpret_cast<u32x4*>(fo + head);
+    const size_t bid = combine_tile<XG>(blockIdx.x, gridDim.x);
+
+    for (size_t t0 = bid * TILE; t0 < nvec; t0 += (size_t)gridDim.x * TILE) {
+        const size_t i0 = t0 + threadIdx.x;
+        if (t0 + TILE <= nvec) {
+            u32x4 a[UNROLL], b[UNROLL];
+            const unsigned off0 = threadIdx.x * 16u;
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                a[u] = ld_pol<POL::in>(vin + i0 + (size_t)u * BLOCK, vin + t0, off0 + (unsigned)u * BLOCK * 16u);
+                b[u] = ld_pol<POL::io>(vio + i0 + (size_t)u * BLOCK, vio + t0, off0 + (unsigned)u * BLOCK * 16u);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) issued_together(a[u], b[u]);
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                st_pol<FST>(vfo + i0 + (size_t)u * BLOCK, vfo + t0, off0 + (unsigned)u * BLOCK * 16u, b[u]);
+                st_pol<POL::st>(vio + i0 + (size_t)u * BLOCK, vio + t0, off0 + (unsigned)u * BLOCK * 16u,
+                                fetch_apply_vec<OP, VT>(b[u], a[u]));
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                const size_t i = i0 + (size_t)u * BLOCK;
+                if (i < nvec) {
+                    u32x4 x = vin[i], y = vio[i];
+                    issued_together(x, y);
+                    vfo[i] = y;
+                    vio[i] = fetch_apply_vec<OP, VT>(y, x);
+                }
+            }
+        }
+    }
+
+    const size_t nscalar = head + tail;
+    if (nscalar) {
+        const size_t body_end = head + nvec * EPV;
+        for (size_t s = (size_t)blockIdx.x * BLOCK + threadIdx.x; s < nscalar;
+             s += (size_t)gridDim.x * BLOCK) {
+            const size_t e = s < head ? s : body_end + (s - head);
+            const T old = io[e];
+            fo[e] = old;
+            io[e] = fetch_apply<OP, T>(old, in[e]);
+        }
+    }
+}
+
+// The `fetched` store of the DRAM-regime fetch kernel (k_fetch_combine_dram and
+// the probe library's default_fetch_probe): non-temporal.  Nothing in the call
+// reads `fetched`, and a store that stays out of the caches leaves them to the
+// two operands that are read; the table is at k_fetch_combine_dram.
+constexpr StPol kFetchDramSt = StPol::nt;
+template <int OP, class T, class VT, int BLOCK>
+__device__ __forceinline__ void fetch_dram_body(const T* __restrict__ in, T* __restrict__ io, T* __restrict__ fo,
+                                                size_t head, size_t nvec, size_t tail)
+{
+    fetch_body<OP, T, VT, 1, BLOCK, kDramRun, DramPolicy<true>, kFetchDramSt>(in, io, fo, head, nvec, tail);
+}
+
 // Operand split of the vector body: head scalars up to 16-byte alignment,
 // whole 16-byte vectors, tail scalars.  Operands whose alignments disagree
 // (or 16-byte elements off 16-byte alignment) are all-scalar here; the
@@ -180,6 +271,20 @@ __host__ inline void combine_split(const void* in, const void* io, size_t count,
     const size_t rest = count - h;
     const size_t epv = 16 / ES;
     head = h; nvec = rest / epv; tail = rest - nvec * epv;
+}
+
+// combine_split for three operands: the vector body runs when all three share
+// one offset from 16-byte alignment; otherwise the whole call is scalar (there
+// is no realigning fetch kernel).
+template <class T>
+__host__ inline void fetch_split(const void* in, const void* io, const void* fo, size_t count, size_t& head,
+                                 size_t& nvec, size_t& tail)
+{
+    if (((uintptr_t)fo & 15) != ((uintptr_t)io & 15) || ((uintptr_t)fo % sizeof(T)) != 0) {
+        head = count; nvec = 0; tail = 0;
+        return;
+    }
+    combine_split<T>(in, io, count, head, nvec, tail);
 }
 
 }  // namespace dev

@@ -35,6 +35,11 @@ hipError_t launch_dt_acc2(int opidx, Kind k, const DevLayout& Lo, const void* or
                           void* target, int64_t n, int align, hipStream_t s);
 hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target,
                            int64_t bytes, int G, hipStream_t s);
+// msx_acc3.hip
+hipError_t launch_dt_gacc3(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lr,
+                           void* result, const DevLayout& Lt, void* target, int64_t n, int align, hipStream_t s);
+hipError_t launch_dt_xchg3(const DevLayout& Lo, const void* origin, const DevLayout& Lr, void* result,
+                           const DevLayout& Lt, void* target, int64_t bytes, int G, hipStream_t s);
 
 namespace {
 
@@ -1316,6 +1321,132 @@ int dt_acc2_dev(int opidx, const Dtype* otc, int64_t ocount, const void* origin,
                              : launch_dt_acc2(opidx, ti->kind, ot->dev, origin, tt->dev, target, p.bytes / ti->size,
                                               align, s);
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout datatype accumulate");
+}
+
+// Checks 4 - 6 of msx_get_accumulate_dev (msx.h) and the path the call takes: a
+// pure function of the host-side types, the counts and the op.  `ot` is null
+// under MPI_NO_OP, where the result triple counts the elements.
+int dt_gacc3_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* rt, int64_t rcount, const Dtype* tt,
+                  int64_t tcount, Acc3Plan* p)
+{
+    *p = Acc3Plan();
+    const int64_t lim = (int64_t)1 << 62;
+    for (const auto& tc : {std::make_pair(ot, ocount), std::make_pair(rt, rcount), std::make_pair(tt, tcount)})
+        if (tc.first && tc.first->size > 0 && tc.second > lim / tc.first->size) {
+            set_error("count overflows the data size");
+            return MPI_ERR_COUNT;
+        }
+    const Dtype* nt = ot ? ot : rt;                      // the triple that counts the elements
+    const int64_t nbytes = (ot ? ocount : rcount) * nt->size;
+    const int64_t rbytes = rcount * rt->size, tbytes = tcount * tt->size;
+    if (nbytes > tbytes) {
+        set_error("accumulate truncated: %lld origin bytes into %lld", (long long)nbytes, (long long)tbytes);
+        return MPI_ERR_TRUNCATE;
+    }
+    if (nbytes > rbytes) {
+        set_error("get_accumulate truncated: %lld target bytes into %lld of the result", (long long)nbytes,
+                  (long long)rbytes);
+        return MPI_ERR_TRUNCATE;
+    }
+    p->elements = nt->el_size > 0 ? nbytes / nt->el_size : (ot ? ocount : rcount) * nt->n_elements;
+    p->bytes = nbytes;
+    if (nbytes == 0) return MPI_SUCCESS;
+    if (opidx == O_NOOP) {
+        p->granule = std::min(layout_align(rt), layout_align(tt));
+    } else if (opidx == O_REPLACE) {
+        p->granule = std::min({layout_align(ot), layout_align(rt), layout_align(tt)});
+    } else {
+        const Dtype* side[3] = {ot, rt, tt};
+        const char* name[3] = {"origin", "result", "target"};
+        for (int i = 0; i < 3; ++i)
+            if (side[i]->eltype == MPI_DATATYPE_NULL) {
+                set_error("%s datatype has no single basic element type", name[i]);
+                return MPI_ERR_TYPE;
+            }
+        const TypeInfo* ti = type_info(tt->eltype);
+        for (int i = 0; i < 2; ++i) {
+            const TypeInfo* xi = type_info(side[i]->eltype);
+            if ((xi ? xi->kind : K_NONE) != (ti ? ti->kind : K_NONE)) {
+                set_error("%s elements 0x%x and target elements 0x%x differ in kind", name[i], side[i]->eltype,
+                          tt->eltype);
+                return MPI_ERR_TYPE;
+            }
+        }
+        for (const Dtype* x : side)
+            if (!type_info(x->eltype) || op_check_dtype(opidx, x->eltype) != MPI_SUCCESS) {
+                set_error("%s is not defined for datatype 0x%x", op_name(opidx), x->eltype);
+                return MPI_ERR_OP;
+            }
+        for (const Dtype* x : side)
+            if (!runs_hold_elements(x, ti->size)) {
+                set_error("datatype runs split elements of 0x%x", x->eltype);
+                return MPI_ERR_TYPE;
+            }
+        p->granule = ti->size;
+    }
+    int64_t d;
+    const bool oc = !ot || contiguous_prefix(ot, nbytes, &d);
+    const bool all = oc && contiguous_prefix(rt, nbytes, &d) && contiguous_prefix(tt, nbytes, &d);
+    p->path = all ? 1 : (opidx == O_NOOP ? 2 : 3);
+    return MPI_SUCCESS;
+}
+
+int dt_gacc3_dev(int opidx, const Dtype* otc, const void* origin, const Dtype* rtc, int64_t rcount, void* result,
+                 const Dtype* ttc, void* target, const Acc3Plan& p, hipStream_t s)
+{
+    if (p.path == 0) return MPI_SUCCESS;
+    if (p.path == 1) {
+        int64_t od = 0, rd = 0, td = 0;
+        if (otc) (void)contiguous_prefix(otc, p.bytes, &od);
+        (void)contiguous_prefix(rtc, p.bytes, &rd);
+        (void)contiguous_prefix(ttc, p.bytes, &td);
+        char* res = static_cast<char*>(result) + rd;
+        char* dst = static_cast<char*>(target) + td;
+        hipError_t e;
+        if (opidx == O_NOOP) {
+            const void* ps = dst;
+            void* pd = res;
+            const size_t nb = (size_t)p.bytes;
+            e = launch_copy_segs(&ps, &pd, &nb, 1, s);
+        } else {
+            const char* src = static_cast<const char*>(origin) + od;
+            const TypeInfo* ti = type_info(ttc->eltype);      // an op's element (checked by the plan)
+            e = opidx == O_REPLACE ? launch_fetch_combine(opidx, K_U8, src, res, dst, (size_t)p.bytes, s)
+                                   : launch_fetch_combine(opidx, ti->kind, src, res, dst, (size_t)(p.bytes / ti->size), s);
+        }
+        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "fetch-and-combine kernel launch");
+    }
+    if (p.path == 2) {
+        // MPI_NO_OP: the typed -> typed copy target -> result.  Over whole target
+        // instances it is msx_accumulate_dev's plan; a prefix that ends inside
+        // an instance is what only the two-layout kernel covers.
+        Acc2Plan q;
+        if (p.bytes % ttc->size == 0) {
+            const int rc = dt_acc2_plan(O_REPLACE, ttc, p.bytes / ttc->size, rtc, rcount, &q);
+            if (rc != MPI_SUCCESS) return rc;
+        } else {
+            q.bytes = p.bytes;
+            q.path = 4;
+        }
+        return dt_acc2_dev(O_REPLACE, ttc, p.bytes / ttc->size, target, rtc, result, q, s);
+    }
+    Dtype* lay[3] = {const_cast<Dtype*>(otc), const_cast<Dtype*>(rtc), const_cast<Dtype*>(ttc)};
+    int rc = MPI_SUCCESS;
+    {
+        std::lock_guard<std::recursive_mutex> g(g_mu);
+        for (int i = 0; i < 3 && rc == MPI_SUCCESS; ++i) rc = build_dev_layout(lay[i]);
+    }
+    if (rc != MPI_SUCCESS) return rc;
+    const int align = (int)std::min<int64_t>({(int64_t)lay[0]->dev.align, (int64_t)lay[1]->dev.align,
+                                              (int64_t)lay[2]->dev.align, ptr_align(origin), ptr_align(result),
+                                              ptr_align(target)});
+    const TypeInfo* ti = type_info(ttc->eltype);
+    const hipError_t e =
+        opidx == O_REPLACE
+            ? launch_dt_xchg3(lay[0]->dev, origin, lay[1]->dev, result, lay[2]->dev, target, p.bytes, align, s)
+            : launch_dt_gacc3(opidx, ti->kind, lay[0]->dev, origin, lay[1]->dev, result, lay[2]->dev, target,
+                              p.bytes / ti->size, align, s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "three-layout datatype get-accumulate");
 }
 
 int dt_pack_any(const Dtype* t, int64_t count, const void* typed, void* packed)

@@ -148,6 +148,26 @@ int dt_acc2_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const D
 int dt_acc2_dev(int opidx, const Dtype* origin_t, int64_t origin_count, const void* origin,
                 const Dtype* target_t, void* target, const Acc2Plan& plan, hipStream_t s);
 
+// msx_get_accumulate_dev (msx.h): result elem e = target elem e, then target
+// elem e = origin elem e (op) target elem e, over THREE type maps.
+// dt_gacc3_plan runs the call's checks 4 - 6 on the host-side types (no GPU is
+// touched); origin_t is null under MPI_NO_OP, where the result triple counts
+// the elements.  dt_gacc3_dev does what the plan says: path 1 is the fetch
+// kernel of msx_fetch.hip (the engine copy for MPI_NO_OP) on the three pieces,
+// path 2 (MPI_NO_OP) dt_acc2_dev's typed -> typed copy target -> result, path 3
+// the three-layout kernel of msx_acc3.hip.
+struct Acc3Plan {
+    int64_t elements = 0;   // basic elements of the call (n)
+    int64_t bytes = 0;      // their data bytes
+    int path = 0;           // 0 nothing to do, 1 - 3 as in msx.h
+    int granule = 0;        // bytes one work item moves (16-byte aligned bases)
+};
+int dt_gacc3_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const Dtype* result_t,
+                  int64_t result_count, const Dtype* target_t, int64_t target_count, Acc3Plan* plan);
+int dt_gacc3_dev(int opidx, const Dtype* origin_t, const void* origin, const Dtype* result_t,
+                 int64_t result_count, void* result, const Dtype* target_t, void* target, const Acc3Plan& plan,
+                 hipStream_t s);
+
 // Blocking forms that accept host (pageable or pinned) or device buffers.
 int dt_pack_any(const Dtype* t, int64_t count, const void* typed, void* packed);
 int dt_unpack_any(const Dtype* t, int64_t count, const void* packed, void* typed);

@@ -692,6 +692,70 @@ MSX_EXPORT int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_
     return dt_acc2_dev(r.opidx, ot, origin_count, origin, tt, target, plan, static_cast<hipStream_t>(stream));
 }
 
+// ---- msx_get_accumulate_dev: fetch and combine between three datatype layouts ----
+// Checks 1 - 6 of msx.h in their order and, when they pass, the plan.  One
+// function behind the plan entry and the real call; it never touches a GPU.
+// *ot stays null under MPI_NO_OP: the origin triple is ignored there.
+static int get_accumulate_plan(int64_t ocount, MPI_Datatype odt, int64_t rcount, MPI_Datatype rdt, int64_t tcount,
+                               MPI_Datatype tdt, MPI_Op op, OpRef* r, Dtype** ot, Dtype** rt, Dtype** tt,
+                               Acc3Plan* plan)
+{
+    const bool noop = op == MPI_NO_OP;
+    if ((!noop && ocount < 0) || rcount < 0 || tcount < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
+    const MPI_Datatype dts[3] = {odt, rdt, tdt};
+    Dtype** out[3] = {ot, rt, tt};
+    *ot = nullptr;
+    for (int i = noop ? 1 : 0; i < 3; ++i) {
+        int rc = v_handle(dts[i], out[i]);
+        if (rc != MPI_SUCCESS) return rc;
+        if (dtype_is_derived(dts[i]) && !(*out[i])->committed) {
+            set_error("datatype 0x%x is not committed", dts[i]);
+            return MPI_ERR_TYPE;
+        }
+    }
+    int rc = v_op_handle(op, r);
+    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(*r, "msx_get_accumulate_dev (one combine per element: use MPI_SUM)");
+    if (rc != MPI_SUCCESS) return rc;
+    if (r->opidx == O_NULL) { set_error("msx_get_accumulate_dev takes builtin ops only"); return MPI_ERR_OP; }
+    return dt_gacc3_plan(r->opidx, *ot, ocount, *rt, rcount, *tt, tcount, plan);
+}
+
+MSX_EXPORT int msx_get_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type, int64_t result_count,
+                                       MPI_Datatype result_type, int64_t target_count, MPI_Datatype target_type,
+                                       MPI_Op op, int64_t* elements, int* path, int* granule)
+{
+    if (!elements || !path || !granule) { set_error("null plan output"); return MPI_ERR_ARG; }
+    *elements = 0;
+    *path = *granule = 0;
+    OpRef r;
+    Dtype *ot, *rt, *tt;
+    Acc3Plan plan;
+    const int rc = get_accumulate_plan(origin_count, origin_type, result_count, result_type, target_count,
+                                       target_type, op, &r, &ot, &rt, &tt, &plan);
+    if (rc != MPI_SUCCESS) return rc;
+    *elements = plan.elements;
+    *path = plan.path;
+    *granule = plan.path ? plan.granule : 0;
+    return MPI_SUCCESS;
+}
+
+MSX_EXPORT int msx_get_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
+                                      void* result, int64_t result_count, MPI_Datatype result_type, void* target,
+                                      int64_t target_count, MPI_Datatype target_type, MPI_Op op, void* stream)
+{
+    OpRef r;
+    Dtype *ot, *rt, *tt;
+    Acc3Plan plan;
+    int rc = get_accumulate_plan(origin_count, origin_type, result_count, result_type, target_count, target_type, op,
+                                 &r, &ot, &rt, &tt, &plan);
+    if (rc != MPI_SUCCESS || plan.path == 0) return rc;
+    if (!result || !target || (!origin && r.opidx != O_NOOP)) { set_error("null buffer"); return MPI_ERR_BUFFER; }
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    return dt_gacc3_dev(r.opidx, ot, origin, rt, result_count, result, tt, target, plan,
+                        static_cast<hipStream_t>(stream));
+}
+
 // ---- PMPI_ profiling aliases --------------------------------------------------
 MSX_ALIAS(MPI_Type_contiguous) int PMPI_Type_contiguous(int, MPI_Datatype, MPI_Datatype*);
 MSX_ALIAS(MPI_Type_vector) int PMPI_Type_vector(int, int, int, MPI_Datatype, MPI_Datatype*);

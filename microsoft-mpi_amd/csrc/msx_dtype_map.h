@@ -1,6 +1,7 @@
 // msx_dtype_map.h — the O(1) address map of a committed datatype layout, shared
 // by the datatype kernels' units (msx_pack.hip: one typed side and a packed
-// stream; msx_acc2.hip: a typed layout on both sides).
+// stream; msx_acc2.hip: a typed layout on both sides; msx_acc3.hip: on all
+// three operands of a get-accumulate).
 //
 //   packed byte p of instance i  ->  typed[i*extent + disp[k] + (p - poff[k])]
 //
@@ -104,6 +105,15 @@ __device__ __forceinline__ int64_t typed_off(const CopyArgs& a, int64_t g)
         const int64_t k = find_run(a.poff, a.nruns, qb);
         return i * a.extent + a.disp[k] + (qb - a.poff[k]);
     }
+}
+
+// Byte offset of granule g in either kind of layout (the units with a layout on
+// every side: msx_acc2.hip, msx_acc3.hip).
+template <int G, bool NARROW>
+__device__ __forceinline__ int64_t map_off(const CopyArgs& a, int64_t g)
+{
+    if (a.poff) return typed_off<G, false, NARROW>(a, g);      // uniform: a kernel argument
+    return typed_off<G, true, NARROW>(a, g);
 }
 
 // Granules per lane in flight: every lane issues kUnroll independent loads

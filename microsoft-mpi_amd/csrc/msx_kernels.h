@@ -31,6 +31,18 @@ struct LaunchCfg {
 hipError_t launch_combine(int opidx, Kind k, const void* in, void* inout, size_t count,
                           hipStream_t s, const LaunchCfg& cfg);
 
+// Bytes per operand above which launch_combine (and launch_fetch_combine) take
+// their DRAM-regime kernels (msx_kernels.hip; MSX_TEST_COMBINE_DRAM_MIN).
+size_t combine_dram_min();
+
+// The fetch form of the combine in ONE launch (msx_fetch.hip; msx.h,
+// msx_fetch_and_op_dev): fetched[i] = inout[i], inout[i] = op(inout[i], in[i])
+// for i in [0, count), launch_combine's geometry by size.  opidx may also be
+// O_REPLACE (inout[i] = in[i]; k names the element size only).  `fetched`
+// meets neither other operand.
+hipError_t launch_fetch_combine(int opidx, Kind k, const void* in, void* fetched, void* inout, size_t count,
+                                hipStream_t s);
+
 // Many independent combines of one (op, kind) in ONE launch (k_combine_segs,
 // msx_combine_segs.hip): segment i is inout[i] = op(inout[i], in[i]) over
 // `count` elements, the bytes launch_combine gives.  At most

@@ -251,13 +251,6 @@ __global__ __launch_bounds__(256) void k_push_wait(CopySegs c, PostFlags f, unsi
 // =====================================================================================
 // host-side dispatch
 // =====================================================================================
-namespace {
-
-using namespace dev;
-
-constexpr int kBlock = 256;
-constexpr int kUnroll = 1;
-
 // Bytes per operand above which the device combine takes k_combine_dram:
 // 16 MiB, where the two operands outgrow the
 // chip's L2 (8 x 4 MiB).  Rounds 1-4 switched only above the 256 MiB Infinity
@@ -282,6 +275,13 @@ size_t combine_dram_min()
     }();
     return v;
 }
+
+namespace {
+
+using namespace dev;
+
+constexpr int kBlock = 256;
+constexpr int kUnroll = 1;
 
 // The realigning path (k_combine_shift): both operands element-aligned but
 // at different offsets from 16-byte alignment, and at least 3 vectors.

@@ -194,6 +194,10 @@ def lib():
         "msx_unpack_dev": (i, [p, i64, i, p, p]),
         "msx_accumulate_dev": (i, [p, i64, i, p, i64, i, i, p]),
         "msx_accumulate_plan": (i, [i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i), ctypes.POINTER(i)]),
+        "msx_fetch_and_op_dev": (i, [p, p, p, i64, i, i, p]),
+        "msx_get_accumulate_dev": (i, [p, i64, i, p, i64, i, p, i64, i, i, p]),
+        "msx_get_accumulate_plan": (i, [i64, i, i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i),
+                                        ctypes.POINTER(i)]),
         "msx_reduce_tree_dev": (i, [ctypes.POINTER(p), i, p, i64, i, i, p]),
         "msx_tune_pack": (i, [i]),
         "msx_copy_dev": (i, [p, p, i64, p]),

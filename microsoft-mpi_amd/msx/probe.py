@@ -1,7 +1,8 @@
 """msx.probe — ctypes binding of libmsx_probe.so, the bench-only measurement
 kernels (microsoft-mpi_amd/probe/msx_probe.hip): HBM stream-mix probes and the
 fp32 SUM combine body in other launch geometries and with other cache policies
-per stream (in_<in load>_io_<inout load>_st_<inout store>).  Used by bench.py, the
+per stream (in_<in load>_io_<inout load>_st_<inout store>), and the fetch form of
+that body per policy of its second store (fetched_st_<policy>).  Used by bench.py, the
 scripts and the GPU tests that check the variants compute the same bits; the
 product library libmsmpi_mi355x.so neither contains nor loads any of it.
 """
@@ -34,6 +35,9 @@ def lib():
                             ("msxp_variant_count", i, []),
                             ("msxp_variant_name", ctypes.c_char_p, [i]),
                             ("msxp_variant_run", i, [i, p, p, i64, p]),
+                            ("msxp_fetch_count", i, []),
+                            ("msxp_fetch_name", ctypes.c_char_p, [i]),
+                            ("msxp_fetch_run", i, [i, p, p, p, i64, p]),
                             ("msxp_tree8", i, [ctypes.POINTER(p), p, i64, i, p]),
                             ("msxp_spin_mark", i, [i64, p, ctypes.c_uint, p])):
         fn = getattr(L, name)
@@ -48,3 +52,11 @@ def variants():
     default DRAM-regime body under its probe symbol)."""
     L = lib()
     return {L.msxp_variant_name(v).decode(): v for v in range(L.msxp_variant_count())}
+
+
+def fetch_variants():
+    """{name: index} of the fp32 SUM fetch-and-combine variants (index 0 = the
+    product's DRAM-regime fetch body under its probe symbol; fetched_st_<policy>
+    = the same body with that cache policy on the store of `fetched`)."""
+    L = lib()
+    return {L.msxp_fetch_name(v).decode(): v for v in range(L.msxp_fetch_count())}

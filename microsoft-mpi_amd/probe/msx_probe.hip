@@ -13,6 +13,9 @@
 //     symbol (k_probe_combine<..., 64, ..., -1>) so single cold-cache launches
 //     stay out of the headline kernel's rocprof statistics, and the same
 //     geometry with every cache policy per stream (k_probe_combine_pol);
+//   * msxp_fetch_*: the fp32 SUM fetch body (fetched[i] = inout[i], inout[i] +=
+//     in[i]; the device code of k_fetch_combine_dram) under its own symbol and
+//     with each cache policy for the `fetched` store (k_probe_fetch_pol);
 //   * msxp_tree8: the product's 8-source DRAM-regime tree (k_tree, fp32 SUM,
 //     non-temporal loads, one-wave workgroups) in another tile order.
 #include <hip/hip_runtime.h>
@@ -94,6 +97,25 @@ __global__ __launch_bounds__(64) void k_probe_combine_pol(const float* __restric
     combine_body<O_SUM, float, float, 1, 64, true, false, kDramRun, CombinePolicy<IN, IO, ST>>(in, io, head, nvec, tail);
 }
 
+// The DRAM-regime fetch body (fetch_body: fetched[i] = inout[i], inout[i] +=
+// in[i]; k_fetch_combine_dram's geometry and combine policy) with each cache
+// policy for the store of `fetched`.
+template <StPol FST>
+__global__ __launch_bounds__(64) void k_probe_fetch_pol(const float* __restrict__ in, float* __restrict__ io,
+                                                        float* __restrict__ fo, size_t head, size_t nvec, size_t tail)
+{
+    fetch_body<O_SUM, float, float, 1, 64, kDramRun, DramPolicy<true>, FST>(in, io, fo, head, nvec, tail);
+}
+
+// default_fetch_probe: exactly what k_fetch_combine_dram<3, float, float, 64>
+// runs (fetch_dram_body, kFetchDramSt included), under this symbol
+__global__ __launch_bounds__(64) void k_probe_fetch_default(const float* __restrict__ in, float* __restrict__ io,
+                                                            float* __restrict__ fo, size_t head, size_t nvec,
+                                                            size_t tail)
+{
+    fetch_dram_body<O_SUM, float, float, 64>(in, io, fo, head, nvec, tail);
+}
+
 // the "LDS staging of the incoming chunk" form: `in` goes global -> LDS ->
 // registers.  Each element is used once, so the stage only adds an LDS write
 // + read per byte and a barrier (measured, not asserted)
@@ -168,6 +190,36 @@ hipError_t run_variant_lds(const void* in, void* io, size_t count, hipStream_t s
                        static_cast<const float*>(in), static_cast<float*>(io), head, nvec, tail);
     return hipGetLastError();
 }
+
+template <class K>
+hipError_t run_fetch_variant(K kernel, const void* in, void* fo, void* io, size_t count, hipStream_t s)
+{
+    size_t head, nvec, tail;
+    fetch_split<float>(in, io, fo, count, head, nvec, tail);
+    size_t grid = (nvec + 63) / 64;
+    const size_t sc = (head + tail + 63) / 64;
+    if (grid < sc) grid = sc;
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64), 0, s, static_cast<const float*>(in),
+                       static_cast<float*>(io), static_cast<float*>(fo), head, nvec, tail);
+    return hipGetLastError();
+}
+
+typedef void (*FetchKernel)(const float*, float*, float*, size_t, size_t, size_t);
+struct FetchVariant {
+    const char* name;
+    FetchKernel kernel;
+};
+// index 0: the product's DRAM-regime fetch body under the probe symbol
+const FetchVariant kFetchVariants[] = {
+    {"default_fetch_probe", k_probe_fetch_default},
+    {"fetched_st_plain", k_probe_fetch_pol<StPol::plain>},
+    {"fetched_st_nt", k_probe_fetch_pol<StPol::nt>},
+    {"fetched_st_sc1", k_probe_fetch_pol<StPol::sc1>},
+    {"fetched_st_sc0sc1", k_probe_fetch_pol<StPol::sc0_sc1>},
+};
+constexpr int kNumFetchVariants = (int)(sizeof(kFetchVariants) / sizeof(kFetchVariants[0]));
 
 struct Variant {
     const char* name;
@@ -271,6 +323,22 @@ MSXP_EXPORT int msxp_variant_run(int v, const void* in, void* inout, int64_t cou
 {
     if (v < 0 || v >= kNumVariants || count < 0 || !in || !inout) return 1;
     return kVariants[v].fn(in, inout, (size_t)count, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : 2;
+}
+
+MSXP_EXPORT int msxp_fetch_count(void) { return kNumFetchVariants; }
+
+MSXP_EXPORT const char* msxp_fetch_name(int v)
+{
+    return v >= 0 && v < kNumFetchVariants ? kFetchVariants[v].name : nullptr;
+}
+
+// fetched[i] = inout[i], inout[i] += in[i] over `count` fp32, variant v, on
+// `stream`; `fetched` meets neither other operand
+MSXP_EXPORT int msxp_fetch_run(int v, const void* in, void* fetched, void* inout, int64_t count, void* stream)
+{
+    if (v < 0 || v >= kNumFetchVariants || count < 0 || !in || !fetched || !inout) return 1;
+    return run_fetch_variant(kFetchVariants[v].kernel, in, fetched, inout, (size_t)count,
+                             static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : 2;
 }
 
 // out[i] = ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)) over n fp32 (16-byte aligned

@@ -371,6 +371,75 @@ int msx_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type,
                         int64_t target_count, MPI_Datatype target_type, MPI_Op op,
                         int64_t* elements, int* path, int* granule);
 
+/* Many msx_accumulate_dev calls of one builtin op in as few launches as
+ * possible: the six typed accumulates of a 3-D block's halo sum in one launch.
+ * All six arrays are HOST arrays of nseg entries; segment i is the origin
+ * triple (origin[i], origin_count[i], origin_type[i]) into the target triple
+ * (target[i], target_count[i], target_type[i]) on device pointers.  The call
+ * is stream-ordered on `stream` and returns after the enqueue; the arrays are
+ * read during the call only (the descriptors travel in the kernel arguments),
+ * so the caller may overwrite them as soon as it returns.  It allocates nothing
+ * and never synchronises (only the first GPU use of a type with an irregular
+ * type map uploads its run table, once, as with msx_pack_dev).
+ * The value: once the stream has drained, segment i's target holds exactly the
+ * bytes
+ *     msx_accumulate_dev(origin[i], origin_count[i], origin_type[i], target[i],
+ *                        target_count[i], target_type[i], op, stream)
+ * would have produced, and no other byte of device memory is written.
+ * Segments are unordered among themselves.  The call is defined when no
+ * target-mapped byte among a segment's n elements is a target-mapped or
+ * origin-mapped byte of another segment, and each segment alone meets
+ * msx_accumulate_dev's own condition.  Origins may overlap each other freely,
+ * and spans may interleave (six faces of one array have overlapping spans and
+ * disjoint maps), so spans are not compared; only check 9 looks at addresses.
+ * Every builtin op msx_accumulate_dev accepts, MPI_REPLACE and MPI_NO_OP
+ * included; user ops, host or device, and MSX_SUM_WIDE are MPI_ERR_OP.  For any
+ * op except MPI_REPLACE / MPI_NO_OP all non-empty segments share one basic
+ * element kind (one (op, kind) kernel runs per launch).
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure; msx_last_error() names the
+ * segment index of every per-segment failure:
+ *   1. nseg == 0: success;
+ *   2. nseg < 0 or any of the six arrays null: MPI_ERR_ARG;
+ *   3. any count negative: MPI_ERR_COUNT;
+ *   4. any datatype invalid or uncommitted: MPI_ERR_TYPE;
+ *   5. an invalid op handle, a user op or MSX_SUM_WIDE: MPI_ERR_OP;
+ *   6. per segment in index order, msx_accumulate_dev's checks 4 - 6:
+ *      truncation MPI_ERR_TRUNCATE (data bytes beyond 2^62: MPI_ERR_COUNT); a
+ *      segment with zero origin data bytes is empty and skipped from here on,
+ *      its pointers never looked at; under MPI_NO_OP the call now succeeds;
+ *      otherwise the element-type rules with msx_accumulate_dev's classes;
+ *   7. for an op other than MPI_REPLACE, two non-empty segments of different
+ *      element kinds: MPI_ERR_TYPE, naming both segments;
+ *   8. a null origin or target of a non-empty segment: MPI_ERR_BUFFER;
+ *   9. two non-empty segments with the same target address and the same target
+ *      datatype handle (they certainly collide): MPI_ERR_BUFFER, naming both;
+ *  10. no GPU: MPI_ERR_OTHER.
+ * With nseg == 1 this is msx_accumulate_dev's class for every failing
+ * argument set.
+ * A non-empty segment is fused when its origin data bytes are below
+ * *fuse_below and the 32-bit address map can hold it (both types' data sizes
+ * below 4 GiB per instance), whatever path msx_accumulate_plan names for it: a
+ * contiguous side is a layout of one run.  Fused segments fill launches in
+ * index order, *width at a time; every other segment is launched on its own
+ * where it stands, exactly as msx_accumulate_dev launches it.
+ *
+ * msx_accumulate_batch_plan runs checks 1 - 7 and reports what the call would
+ * do, without ever initialising a GPU (a pure function of its arguments; it
+ * takes no addresses): *width the most segments one fused launch carries,
+ * *fuse_below the data-byte limit below which a segment is fused, *batched the
+ * segments in fused launches, *single the segments launched on their own,
+ * *launches = ceil(*batched / *width) + *single.  Empty segments count in
+ * neither.  A null output pointer is MPI_ERR_ARG.  The call itself dispatches
+ * on the same plan. */
+int msx_accumulate_batch_dev(const void* const* origin, const int64_t* origin_count, const MPI_Datatype* origin_type,
+                             void* const* target, const int64_t* target_count, const MPI_Datatype* target_type,
+                             int nseg, MPI_Op op, void* stream);
+int msx_accumulate_batch_plan(const int64_t* origin_count, const MPI_Datatype* origin_type,
+                              const int64_t* target_count, const MPI_Datatype* target_type,
+                              int nseg, MPI_Op op,
+                              int* width, int64_t* fuse_below, int* launches, int* batched, int* single);
+
 /* The combine that also hands back the old value, in ONE launch:
  * MPI_Fetch_and_op's value on device pointers, with no window.  For i < count:
  *     fetched[i] = inout[i]              (the old bytes, copied whole, the

@@ -25,9 +25,17 @@
 // No __restrict__ on the kernels' operands: the two spans may interleave (two
 // columns of one matrix).  Each lane reads element e of both sides before it
 // stores it, and no other lane touches element e.
+//
+// acc2_elem, the serial tiles and the launch shape (make_launch2) are
+// msx_acc2_dev.h's, shared with msx_acc2_segs.hip.  The whole-tile bodies stay
+// written out in the two kernels here: calling msx_acc2_dev.h's
+// acc2_tile_whole / copy2_tile_whole instead gives the same instructions in
+// another register assignment, and these kernels' machine code is kept as it
+// was (scripts/compare_kernels.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "msx_acc2_dev.h"
 #include "msx_dev_ops.h"
 #include "msx_dtype.h"
 #include "msx_dtype_map.h"
@@ -36,37 +44,6 @@
 
 namespace msx {
 namespace dev {
-
-// target element (op)= origin element; acc_elem's two forms (msx_pack.hip).
-template <int OP, class T, bool ALIGNED>
-__device__ __forceinline__ void acc2_elem(char* t, const char* o)
-{
-    constexpr int E = (int)sizeof(T);
-    if constexpr (ALIGNED) {
-        T* tt = reinterpret_cast<T*>(t);
-        *tt = Fn<OP>::apply(*tt, *reinterpret_cast<const T*>(o));
-    } else {
-        T x, y;
-        __builtin_memcpy(&x, t, E);
-        __builtin_memcpy(&y, o, E);
-        x = Fn<OP>::apply(x, y);
-        __builtin_memcpy(t, &x, E);
-    }
-}
-
-// The elements of one lane, one after the other (not unrolled): the call's last
-// workgroup when its tile is cut by n, and every workgroup of a call too large
-// for the 32-bit divisions.
-template <int OP, class T, bool ALIGNED, bool NARROW>
-__device__ __forceinline__ void acc2_tile_serial(const CopyArgs& o, const CopyArgs& t, int64_t n, int64_t g0)
-{
-    constexpr int E = (int)sizeof(T);
-#pragma unroll 1
-    for (int u = 0; u < kUnroll; ++u) {
-        const int64_t g = g0 + u * 64;
-        if (g < n) acc2_elem<OP, T, ALIGNED>(t.typed + map_off<E, NARROW>(t, g), o.typed + map_off<E, NARROW>(o, g));
-    }
-}
 
 // o.typed / t.typed: the origin and target buffer addresses; n elements.
 template <int OP, class T, bool ALIGNED>
@@ -101,19 +78,6 @@ __global__ __launch_bounds__(64) void k_dt_acc2_tile(CopyArgs o, CopyArgs t, int
     }
 }
 
-template <int G, bool NARROW>
-__device__ __forceinline__ void copy2_tile_serial(const CopyArgs& o, const CopyArgs& t, int64_t n, int64_t g0)
-{
-    typedef typename GranT<G>::T T;
-#pragma unroll 1
-    for (int u = 0; u < kUnroll; ++u) {
-        const int64_t g = g0 + u * 64;
-        if (g < n)
-            *reinterpret_cast<T*>(t.typed + map_off<G, NARROW>(t, g)) =
-                *reinterpret_cast<const T*>(o.typed + map_off<G, NARROW>(o, g));
-    }
-}
-
 // MPI_REPLACE: granule g of the origin's type map to granule g of the
 // target's, G the largest granule both layouts and both pointers allow.
 template <int G>
@@ -137,29 +101,6 @@ __global__ __launch_bounds__(64) void k_dt_copy2_tile(CopyArgs o, CopyArgs t, in
 }
 
 // ---- host side ---------------------------------------------------------------
-// Both maps in granules of G bytes, and the launch shape of n granules.
-struct Launch2 {
-    CopyArgs o, t;
-    int narrow;
-    dim3 grid;
-};
-
-hipError_t make_launch2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target, int64_t n, int G,
-                        Launch2* l)
-{
-    // every run offset / length must hold whole granules for the granule map
-    if (Lo.size % G || Lt.size % G || (Lo.regular && Lo.blen % G) || (Lt.regular && Lt.blen % G))
-        return hipErrorInvalidValue;
-    l->o = make_args(Lo, 1, const_cast<void*>(origin), nullptr, G);
-    l->t = make_args(Lt, 1, target, nullptr, G);
-    // the 32-bit magic divisions hold for g, and every instance, below 2^32 granules
-    l->narrow = n < 0xffffffffll && l->o.gsize < 0xffffffffll && l->t.gsize < 0xffffffffll;
-    const int64_t tiles = (n + 64 * kUnroll - 1) / (64 * kUnroll);
-    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
-    l->grid = dim3((unsigned)tiles);
-    return hipSuccess;
-}
-
 // One (op, element type) pair of msx_op_kind.h's map.
 template <int OP, class T>
 hipError_t run_acc2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target, int64_t n, int align,

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <string>
 
 #include "msx_comm.h"
 #include "msx_kernels.h"
@@ -1321,6 +1322,90 @@ int dt_acc2_dev(int opidx, const Dtype* otc, int64_t ocount, const void* origin,
                              : launch_dt_acc2(opidx, ti->kind, ot->dev, origin, tt->dev, target, p.bytes / ti->size,
                                               align, s);
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout datatype accumulate");
+}
+
+// ---- msx_accumulate_batch_dev: many typed combines in few launches --------------
+int acc2_batch_width() { return kAcc2SegsWidth; }
+int64_t acc2_batch_fuse_below() { return kAcc2SegsFuseBelow; }
+int Acc2BatchPlan::launches() const { return (fused + kAcc2SegsWidth - 1) / kAcc2SegsWidth + single; }
+
+// Checks 6 and 7 of msx_accumulate_batch_dev (msx.h) and what the call does with
+// each non-empty segment: a pure function of the host-side types, the counts
+// and the op.
+int dt_acc2_batch_plan(int opidx, const Dtype* const* ot, const int64_t* ocount, const Dtype* const* tt,
+                       const int64_t* tcount, int nseg, Acc2BatchPlan* plan)
+{
+    *plan = Acc2BatchPlan();
+    for (int i = 0; i < nseg; ++i) {
+        Acc2BatchStep st;
+        const int rc = dt_acc2_plan(opidx, ot[i], ocount[i], tt[i], tcount[i], &st.plan);
+        if (rc != MPI_SUCCESS) {
+            const std::string why = last_error();
+            set_error("segment %d: %s", i, why.c_str());
+            return rc;
+        }
+        if (st.plan.path == 0) continue;      // no origin data bytes, or MPI_NO_OP
+        st.seg = i;
+        st.ot = ot[i];
+        st.tt = tt[i];
+        st.ocount = ocount[i];
+        // The fused kernels divide in 32 bits.  The granule is at least one
+        // byte (MPI_REPLACE's depends on the pointers, which a plan does not
+        // see), so sizes in bytes bound the sizes in granules.
+        st.fused = st.plan.bytes < kAcc2SegsFuseBelow && dt_map_narrow(st.plan.bytes, ot[i]->size, tt[i]->size);
+        plan->steps.push_back(st);
+    }
+    if (opidx != O_REPLACE)
+        for (const Acc2BatchStep& st : plan->steps) {
+            const Acc2BatchStep& s0 = plan->steps[0];
+            if (type_info(st.tt->eltype)->kind != type_info(s0.tt->eltype)->kind) {
+                set_error("segment %d has elements 0x%x and segment %d elements 0x%x: one element kind per call",
+                          s0.seg, s0.tt->eltype, st.seg, st.tt->eltype);
+                return MPI_ERR_TYPE;
+            }
+        }
+    for (const Acc2BatchStep& st : plan->steps) ++(st.fused ? plan->fused : plan->single);
+    return MPI_SUCCESS;
+}
+
+int dt_acc2_batch_dev(int opidx, const Acc2BatchPlan& plan, const void* const* origin, void* const* target,
+                      hipStream_t s)
+{
+    if (plan.steps.empty()) return MPI_SUCCESS;
+    // every fused segment's device layout before the first launch (a single
+    // segment builds its own in dt_acc2_dev)
+    {
+        std::lock_guard<std::recursive_mutex> g(g_mu);
+        for (const Acc2BatchStep& st : plan.steps) {
+            if (!st.fused) continue;
+            int rc = build_dev_layout(const_cast<Dtype*>(st.ot));
+            if (rc == MPI_SUCCESS) rc = build_dev_layout(const_cast<Dtype*>(st.tt));
+            if (rc != MPI_SUCCESS) return rc;
+        }
+    }
+    const Kind k = opidx == O_REPLACE ? K_NONE : type_info(plan.steps[0].tt->eltype)->kind;
+    Acc2Seg segs[kAcc2SegsWidth];
+    int n = 0, left = plan.fused;
+    for (const Acc2BatchStep& st : plan.steps) {
+        const int i = st.seg;
+        if (!st.fused) {
+            const int rc = dt_acc2_dev(opidx, st.ot, st.ocount, origin[i], st.tt, target[i], st.plan, s);
+            if (rc != MPI_SUCCESS) return rc;
+            continue;
+        }
+        // dt_acc2_dev's alignment: both layouts and both pointers
+        const int align = (int)std::min<int64_t>({(int64_t)st.ot->dev.align, (int64_t)st.tt->dev.align,
+                                                  ptr_align(origin[i]), ptr_align(target[i])});
+        segs[n++] = Acc2Seg{&st.ot->dev, origin[i], &st.tt->dev, target[i], st.plan.bytes, align};
+        if (n == kAcc2SegsWidth || n == left) {
+            const hipError_t e = opidx == O_REPLACE ? launch_dt_copy2_segs(segs, n, s)
+                                                    : launch_dt_acc2_segs(opidx, k, segs, n, s);
+            if (e != hipSuccess) return hip_fail(e, "batched two-layout datatype accumulate");
+            left -= n;
+            n = 0;
+        }
+    }
+    return MPI_SUCCESS;
 }
 
 // Checks 4 - 6 of msx_get_accumulate_dev (msx.h) and the path the call takes: a

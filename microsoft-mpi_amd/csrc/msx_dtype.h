@@ -148,6 +148,35 @@ int dt_acc2_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const D
 int dt_acc2_dev(int opidx, const Dtype* origin_t, int64_t origin_count, const void* origin,
                 const Dtype* target_t, void* target, const Acc2Plan& plan, hipStream_t s);
 
+// msx_accumulate_batch_dev (msx.h): nseg independent msx_accumulate_dev calls of
+// one builtin op in as few launches as possible.  dt_acc2_batch_plan runs the
+// call's checks 6 and 7 (dt_acc2_plan per segment in index order, then one
+// element kind for an op) and says what the call does with every non-empty
+// segment: a segment below acc2_batch_fuse_below() data bytes whose two
+// instance sizes the 32-bit address map can hold is fused, up to
+// acc2_batch_width() per launch of msx_acc2_segs.hip's kernels, whatever its
+// dt_acc2_plan path; every other one is dt_acc2_dev's.  dt_acc2_batch_dev does
+// exactly that, in index order.
+struct Acc2BatchStep {
+    int seg = 0;
+    const Dtype* ot = nullptr;
+    const Dtype* tt = nullptr;
+    int64_t ocount = 0;
+    Acc2Plan plan;
+    bool fused = false;
+};
+struct Acc2BatchPlan {
+    std::vector<Acc2BatchStep> steps;   // the non-empty segments, in index order
+    int fused = 0, single = 0;
+    int launches() const;
+};
+int acc2_batch_width();
+int64_t acc2_batch_fuse_below();
+int dt_acc2_batch_plan(int opidx, const Dtype* const* origin_t, const int64_t* origin_count,
+                       const Dtype* const* target_t, const int64_t* target_count, int nseg, Acc2BatchPlan* plan);
+int dt_acc2_batch_dev(int opidx, const Acc2BatchPlan& plan, const void* const* origin, void* const* target,
+                      hipStream_t s);
+
 // msx_get_accumulate_dev (msx.h): result elem e = target elem e, then target
 // elem e = origin elem e (op) target elem e, over THREE type maps.
 // dt_gacc3_plan runs the call's checks 4 - 6 on the host-side types (no GPU is

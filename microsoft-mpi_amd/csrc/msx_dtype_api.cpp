@@ -11,6 +11,8 @@
 #include <limits.h>
 #include <string.h>
 
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/mpi.h"
@@ -690,6 +692,95 @@ MSX_EXPORT int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_
     rc = ensure_device();
     if (rc != MPI_SUCCESS) return rc;
     return dt_acc2_dev(r.opidx, ot, origin_count, origin, tt, target, plan, static_cast<hipStream_t>(stream));
+}
+
+// ---- msx_accumulate_batch_dev: many typed combines in few launches ---------------
+// Checks 2 - 7 of msx.h in their order (2 for the four arrays a plan takes)
+// and, when they pass, the plan.  One function behind the plan entry and the
+// real call; it never touches a GPU.
+static int accumulate_batch_plan(const int64_t* ocount, const MPI_Datatype* odt, const int64_t* tcount,
+                                 const MPI_Datatype* tdt, int nseg, MPI_Op op, OpRef* r, Acc2BatchPlan* plan)
+{
+    if (nseg < 0 || !ocount || !odt || !tcount || !tdt) { set_error("bad segment arrays (nseg=%d)", nseg); return MPI_ERR_ARG; }
+    for (int i = 0; i < nseg; ++i)
+        if (ocount[i] < 0 || tcount[i] < 0) { set_error("negative count in segment %d", i); return MPI_ERR_COUNT; }
+    std::vector<const Dtype*> ot((size_t)nseg), tt((size_t)nseg);
+    for (int i = 0; i < nseg; ++i) {
+        const MPI_Datatype dts[2] = {odt[i], tdt[i]};
+        const Dtype** out[2] = {&ot[(size_t)i], &tt[(size_t)i]};
+        for (int j = 0; j < 2; ++j) {
+            Dtype* t = nullptr;
+            const int rc = v_handle(dts[j], &t);
+            if (rc != MPI_SUCCESS) {
+                const std::string why = last_error();
+                set_error("segment %d: %s", i, why.c_str());
+                return rc;
+            }
+            if (dtype_is_derived(dts[j]) && !t->committed) {
+                set_error("segment %d: datatype 0x%x is not committed", i, dts[j]);
+                return MPI_ERR_TYPE;
+            }
+            *out[j] = t;
+        }
+    }
+    int rc = v_op_handle(op, r);
+    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(*r, "msx_accumulate_batch_dev (one combine per element: use MPI_SUM)");
+    if (rc != MPI_SUCCESS) return rc;
+    if (r->opidx == O_NULL) { set_error("msx_accumulate_batch_dev takes builtin ops only"); return MPI_ERR_OP; }
+    return dt_acc2_batch_plan(r->opidx, ot.data(), ocount, tt.data(), tcount, nseg, plan);
+}
+
+MSX_EXPORT int msx_accumulate_batch_plan(const int64_t* origin_count, const MPI_Datatype* origin_type,
+                                         const int64_t* target_count, const MPI_Datatype* target_type, int nseg,
+                                         MPI_Op op, int* width, int64_t* fuse_below, int* launches, int* batched,
+                                         int* single)
+{
+    if (!width || !fuse_below || !launches || !batched || !single) { set_error("null plan output"); return MPI_ERR_ARG; }
+    *width = acc2_batch_width();
+    *fuse_below = acc2_batch_fuse_below();
+    *launches = *batched = *single = 0;
+    if (nseg == 0) return MPI_SUCCESS;
+    OpRef r;
+    Acc2BatchPlan plan;
+    const int rc = accumulate_batch_plan(origin_count, origin_type, target_count, target_type, nseg, op, &r, &plan);
+    if (rc != MPI_SUCCESS) return rc;
+    *launches = plan.launches();
+    *batched = plan.fused;
+    *single = plan.single;
+    return MPI_SUCCESS;
+}
+
+MSX_EXPORT int msx_accumulate_batch_dev(const void* const* origin, const int64_t* origin_count,
+                                        const MPI_Datatype* origin_type, void* const* target,
+                                        const int64_t* target_count, const MPI_Datatype* target_type, int nseg,
+                                        MPI_Op op, void* stream)
+{
+    if (nseg == 0) return MPI_SUCCESS;
+    if (!origin || !target) { set_error("bad segment arrays (nseg=%d)", nseg); return MPI_ERR_ARG; }
+    OpRef r;
+    Acc2BatchPlan plan;
+    int rc = accumulate_batch_plan(origin_count, origin_type, target_count, target_type, nseg, op, &r, &plan);
+    if (rc != MPI_SUCCESS || plan.steps.empty()) return rc;
+    for (const Acc2BatchStep& st : plan.steps)
+        if (!origin[st.seg] || !target[st.seg]) { set_error("null buffer in segment %d", st.seg); return MPI_ERR_BUFFER; }
+    // two segments with one target address and one target datatype handle map
+    // the same first element: they certainly collide (spans are not compared:
+    // disjoint maps may interleave)
+    std::vector<const Acc2BatchStep*> by_target;
+    for (const Acc2BatchStep& st : plan.steps) by_target.push_back(&st);
+    auto key = [&](const Acc2BatchStep* st) { return std::make_pair((uintptr_t)target[st->seg], target_type[st->seg]); };
+    std::sort(by_target.begin(), by_target.end(), [&](const Acc2BatchStep* a, const Acc2BatchStep* b) {
+        return key(a) != key(b) ? key(a) < key(b) : a->seg < b->seg;
+    });
+    for (size_t j = 1; j < by_target.size(); ++j)
+        if (key(by_target[j]) == key(by_target[j - 1])) {
+            set_error("target of segment %d is the target of segment %d (same address, same datatype)",
+                      by_target[j]->seg, by_target[j - 1]->seg);
+            return MPI_ERR_BUFFER;
+        }
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    return dt_acc2_batch_dev(r.opidx, plan, origin, target, static_cast<hipStream_t>(stream));
 }
 
 // ---- msx_get_accumulate_dev: fetch and combine between three datatype layouts ----

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 #include "msx_types.h"
 
 namespace msx {
@@ -56,6 +57,39 @@ struct CombineSeg {
     size_t count;
 };
 hipError_t launch_combine_segs(int opidx, Kind k, const CombineSeg* segs, int nseg, hipStream_t s);
+
+// The two-layout datatype kernels (msx_acc2.hip, msx_acc2_segs.hip) divide in
+// 32 bits while the call's granule count and both instance sizes, in granules,
+// are below 2^32 (the magic divisions of msx_dtype_map.h).
+constexpr bool dt_map_narrow(int64_t n, int64_t gsize_o, int64_t gsize_t)
+{
+    return n < 0xffffffffll && gsize_o < 0xffffffffll && gsize_t < 0xffffffffll;
+}
+
+// Many independent two-layout combines of one (op, kind) in ONE launch
+// (k_dt_acc2_segs, msx_acc2_segs.hip; msx.h, msx_accumulate_batch_dev):
+// segment i is target element e (op)= origin element e over the first `bytes`
+// data bytes of its origin layout, the bytes launch_dt_acc2 gives.  A
+// contiguous side is a regular layout of one run per instance.  At most
+// kAcc2SegsWidth segments, each below kAcc2SegsFuseBelow data bytes and inside
+// dt_map_narrow; empty segments are skipped.  align: the largest power of two
+// dividing every element address of both sides of the segment (layouts and
+// pointers); the launch runs its aligned form when every segment allows it.
+// launch_dt_copy2_segs is MPI_REPLACE: bytes move in granules of the smallest
+// `align` of the launch.
+struct DevLayout;
+constexpr int kAcc2SegsWidth = 12;
+constexpr int64_t kAcc2SegsFuseBelow = (int64_t)4 << 20;     // measured: DESIGN.md §3b
+struct Acc2Seg {
+    const DevLayout* lo;
+    const void* origin;
+    const DevLayout* lt;
+    void* target;
+    int64_t bytes;
+    int align;
+};
+hipError_t launch_dt_acc2_segs(int opidx, Kind k, const Acc2Seg* segs, int nseg, hipStream_t s);
+hipError_t launch_dt_copy2_segs(const Acc2Seg* segs, int nseg, hipStream_t s);
 
 // Reference-order tree combine over p inputs (p = 1..8):
 //   out[i] = T(srcs[0][i], ..., srcs[p-1][i]) where T is the balanced binary

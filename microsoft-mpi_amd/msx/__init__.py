@@ -194,6 +194,10 @@ def lib():
         "msx_unpack_dev": (i, [p, i64, i, p, p]),
         "msx_accumulate_dev": (i, [p, i64, i, p, i64, i, i, p]),
         "msx_accumulate_plan": (i, [i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i), ctypes.POINTER(i)]),
+        # host arrays of device pointers / counts / datatype handles as void*
+        "msx_accumulate_batch_dev": (i, [p, p, p, p, p, p, i, i, p]),
+        "msx_accumulate_batch_plan": (i, [p, p, p, p, i, i, ctypes.POINTER(i), ctypes.POINTER(i64),
+                                          ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i)]),
         "msx_fetch_and_op_dev": (i, [p, p, p, i64, i, i, p]),
         "msx_get_accumulate_dev": (i, [p, i64, i, p, i64, i, p, i64, i, i, p]),
         "msx_get_accumulate_plan": (i, [i64, i, i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i),

@@ -23,6 +23,9 @@
  *                            (win.cpp:1435, packethandling.cpp:2969-3004) and
  *                            the two-datatype MPIR_Localcopy (mpid/pt2pt.cpp:
  *                            770-948), with a type map on BOTH sides.
+ *   msx_accumulate_widen_dev <- not in the reference: the same MPID_Uop_call on
+ *                            MPI_FLOAT with the origin held as 16-bit floats,
+ *                            widened exactly on the way in.
  *   msx_fetch_and_op_dev /<- the target side of MPI_Fetch_and_op /
  *   msx_get_accumulate_dev   MPI_Get_accumulate (win.cpp:1804,
  *                            Handle_MPIDI_CH3_PKT_GET_ACCUMULATE,
@@ -370,6 +373,71 @@ int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype or
 int msx_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type,
                         int64_t target_count, MPI_Datatype target_type, MPI_Op op,
                         int64_t* elements, int* path, int* granule);
+
+/* A 16-bit float origin accumulated into an fp32 target in one launch: the
+ * accumulator stays in fp32 and each bf16 / fp16 contribution is added as it
+ * comes, rounded once, later, or never.  The triples are MPI_Accumulate's and
+ * the element order is msx_accumulate_dev's.  The origin's basic element type
+ * is MSX_FLOAT16 or MSX_BFLOAT16, the target's a 4-byte float (MPI_FLOAT,
+ * MPI_REAL, MPI_REAL4); each side may be predefined or any committed derived
+ * type over its element type.  Stream-ordered on `stream`; the call returns
+ * after the enqueue, allocates nothing and never synchronises (only the first
+ * GPU use of a type with an irregular type map uploads its run table, once, as
+ * with msx_pack_dev).
+ *
+ * The value.  Let n be the number of basic elements of the origin triple.  For
+ * e < n:
+ *     target[e] = F_op(target[e], W(origin[e]))
+ * the target in the `inout` role.  F_op is the fp32 combine of
+ * msx_reduce_local_dev on MPI_FLOAT (the reference's op.cpp with the x86 NaN
+ * rule for MPI_SUM / MPI_PROD, `inout > in ? inout : in` for MPI_MAX / MPI_MIN).
+ * Ops: MPI_SUM, MPI_PROD, MPI_MAX, MPI_MIN; MPI_REPLACE is target[e] =
+ * W(origin[e]), a typed widening copy; MPI_NO_OP does nothing.  No other byte
+ * of device memory is written.  The target may hold more elements than n: the
+ * rest is untouched, and a last target instance may be partly covered.  The
+ * spans may interleave; the call is defined when no target-mapped byte among
+ * the n elements is an origin-mapped byte and the target map names no location
+ * twice.
+ *
+ * W widens exactly.  As bit patterns, uint16 x to uint32:
+ *   MSX_BFLOAT16: x << 16, for every x;
+ *   MSX_FLOAT16: the exact value for every non-NaN x, subnormals included; for
+ *     a NaN (exponent 31, mantissa m != 0) sign << 31 | 0x7F800000 | m << 13:
+ *     the payload and the signalling state are kept, it is not quieted.
+ * So W is injective and narrowing W(x) gives x back for every non-NaN x.  The
+ * NaN choice shows only where W(origin) itself is stored (MPI_REPLACE, MPI_MAX
+ * / MPI_MIN choosing `in`); MPI_SUM / MPI_PROD quiet whatever NaN they return.
+ *
+ * Checks, all on the host before any GPU is touched, the first failure
+ * deciding the class, nothing enqueued on a failure:
+ *   1. either count negative: MPI_ERR_COUNT;
+ *   2. an invalid or uncommitted datatype: MPI_ERR_TYPE;
+ *   3. an invalid op handle, a user op (host or device), MSX_SUM_WIDE, or any
+ *      builtin op other than the six above: MPI_ERR_OP;
+ *   4. two times the origin's data bytes exceeding the target's data bytes:
+ *      MPI_ERR_TRUNCATE (data bytes beyond 2^62 on either side: MPI_ERR_COUNT);
+ *   5. zero origin data bytes, or MPI_NO_OP: success, the pointers are never
+ *      looked at;
+ *   6. an origin whose basic element type is neither MSX_FLOAT16 nor
+ *      MSX_BFLOAT16, a target whose is not a 4-byte float, a type with no
+ *      single element type (a mixed struct, the pair types), a type map that
+ *      splits an element: MPI_ERR_TYPE;
+ *   7. a null origin or target: MPI_ERR_BUFFER;
+ *   8. no GPU: MPI_ERR_OTHER.
+ *
+ * msx_accumulate_widen_plan runs checks 1 - 6 and reports what the call would
+ * do, without ever initialising a GPU (a pure function of its arguments; the
+ * call itself dispatches on the same plan).  *elements: n.  *path:
+ *   0  nothing to do;
+ *   1  both pieces contiguous: the streaming kernel;
+ *   2  the two-layout kernel (a contiguous side is a layout of one run).
+ * A null output pointer is MPI_ERR_ARG. */
+int msx_accumulate_widen_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
+                             void* target, int64_t target_count, MPI_Datatype target_type,
+                             MPI_Op op, void* stream);
+int msx_accumulate_widen_plan(int64_t origin_count, MPI_Datatype origin_type,
+                              int64_t target_count, MPI_Datatype target_type, MPI_Op op,
+                              int64_t* elements, int* path);
 
 /* Many msx_accumulate_dev calls of one builtin op in as few launches as
  * possible: the six typed accumulates of a 3-D block's halo sum in one launch.

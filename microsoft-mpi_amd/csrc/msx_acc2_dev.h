@@ -140,5 +140,22 @@ inline hipError_t make_launch2(const DevLayout& Lo, const void* origin, const De
     return hipSuccess;
 }
 
+// make_launch2 with a granule per side: element e of the call is granule e of
+// the origin's map in Go bytes and granule e of the target's in Gt bytes (the
+// widening accumulate of msx_widen.hip: 2-byte elements into 4-byte ones).
+inline hipError_t make_launch2g(const DevLayout& Lo, const void* origin, int Go, const DevLayout& Lt, void* target,
+                                int Gt, int64_t n, Launch2* l)
+{
+    if (Lo.size % Go || Lt.size % Gt || (Lo.regular && Lo.blen % Go) || (Lt.regular && Lt.blen % Gt))
+        return hipErrorInvalidValue;
+    l->o = make_args(Lo, 1, const_cast<void*>(origin), nullptr, Go);
+    l->t = make_args(Lt, 1, target, nullptr, Gt);
+    l->narrow = dt_map_narrow(n, l->o.gsize, l->t.gsize);
+    const int64_t tiles = (n + 64 * kUnroll - 1) / (64 * kUnroll);
+    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;
+    l->grid = dim3((unsigned)tiles);
+    return hipSuccess;
+}
+
 }  // namespace dev
 }  // namespace msx

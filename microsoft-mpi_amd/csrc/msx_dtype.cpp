@@ -36,6 +36,9 @@ hipError_t launch_dt_acc2(int opidx, Kind k, const DevLayout& Lo, const void* or
                           void* target, int64_t n, int align, hipStream_t s);
 hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target,
                            int64_t bytes, int G, hipStream_t s);
+// msx_widen.hip (the contiguous form, launch_widen_combine, is in msx_kernels.h)
+hipError_t launch_dt_accw2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
+                           void* target, int64_t n, bool aligned, hipStream_t s);
 // msx_acc3.hip
 hipError_t launch_dt_gacc3(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lr,
                            void* result, const DevLayout& Lt, void* target, int64_t n, int align, hipStream_t s);
@@ -1226,6 +1229,23 @@ bool contiguous_prefix(const Dtype* t, int64_t bytes, int64_t* disp)
     return bytes <= first.len || (single_run(t, &r) && t->size == t->extent);
 }
 
+// Check 6's rule that both types have one basic element type (a mixed struct
+// and the pair types have none), for dt_acc2_plan and dt_accw2_plan.
+int single_element_types(const Dtype* ot, const Dtype* tt)
+{
+    if (ot->eltype != MPI_DATATYPE_NULL && tt->eltype != MPI_DATATYPE_NULL) return MPI_SUCCESS;
+    set_error("%s datatype has no single basic element type", ot->eltype == MPI_DATATYPE_NULL ? "origin" : "target");
+    return MPI_ERR_TYPE;
+}
+
+// Check 6's rule that neither type map splits an element (osz / tsz bytes).
+int elements_whole(const Dtype* ot, int64_t osz, const Dtype* tt, int64_t tsz)
+{
+    if (runs_hold_elements(ot, osz) && runs_hold_elements(tt, tsz)) return MPI_SUCCESS;
+    set_error("datatype runs split elements of 0x%x", tt->eltype);
+    return MPI_ERR_TYPE;
+}
+
 }  // namespace
 
 // Checks 4 - 6 of msx_accumulate_dev (msx.h) and the path the call takes: a pure
@@ -1252,10 +1272,7 @@ int dt_acc2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, in
     } else {
         const TypeInfo* oi = type_info(ot->eltype);
         const TypeInfo* ti = type_info(tt->eltype);
-        if (ot->eltype == MPI_DATATYPE_NULL || tt->eltype == MPI_DATATYPE_NULL) {
-            set_error("%s datatype has no single basic element type", ot->eltype == MPI_DATATYPE_NULL ? "origin" : "target");
-            return MPI_ERR_TYPE;
-        }
+        if (const int rc = single_element_types(ot, tt)) return rc;
         if ((oi ? oi->kind : K_NONE) != (ti ? ti->kind : K_NONE)) {
             set_error("origin elements 0x%x and target elements 0x%x differ in kind", ot->eltype, tt->eltype);
             return MPI_ERR_TYPE;
@@ -1265,10 +1282,7 @@ int dt_acc2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, in
                 set_error("%s is not defined for datatype 0x%x", op_name(opidx), el);
                 return MPI_ERR_OP;
             }
-        if (!runs_hold_elements(ot, oi->size) || !runs_hold_elements(tt, ti->size)) {
-            set_error("datatype runs split elements of 0x%x", tt->eltype);
-            return MPI_ERR_TYPE;
-        }
+        if (const int rc = elements_whole(ot, oi->size, tt, ti->size)) return rc;
         p->granule = ti->size;
     }
     int64_t od, td;
@@ -1322,6 +1336,72 @@ int dt_acc2_dev(int opidx, const Dtype* otc, int64_t ocount, const void* origin,
                              : launch_dt_acc2(opidx, ti->kind, ot->dev, origin, tt->dev, target, p.bytes / ti->size,
                                               align, s);
     return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout datatype accumulate");
+}
+
+// ---- msx_accumulate_widen_dev: 16-bit float origins into fp32 targets ------------
+// Checks 4 - 6 of msx_accumulate_widen_dev (msx.h) and the path the call takes: a
+// pure function of the two host-side types, the counts and the op.
+int dt_accw2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, int64_t tcount, AccW2Plan* p)
+{
+    *p = AccW2Plan();
+    const int64_t lim = (int64_t)1 << 62;
+    if ((ot->size > 0 && ocount > lim / ot->size) || (tt->size > 0 && tcount > lim / tt->size)) {
+        set_error("count overflows the data size");
+        return MPI_ERR_COUNT;
+    }
+    const int64_t obytes = ocount * ot->size, tbytes = tcount * tt->size;
+    if (obytes > tbytes / 2) {      // 2 * obytes > tbytes
+        set_error("widening accumulate truncated: %lld origin bytes (twice that widened) into %lld",
+                  (long long)obytes, (long long)tbytes);
+        return MPI_ERR_TRUNCATE;
+    }
+    p->elements = ot->el_size > 0 ? obytes / ot->el_size : ocount * ot->n_elements;
+    p->bytes = obytes;
+    if (obytes == 0 || opidx == O_NOOP) return MPI_SUCCESS;
+    if (const int rc = single_element_types(ot, tt)) return rc;
+    const TypeInfo* oi = type_info(ot->eltype);
+    const TypeInfo* ti = type_info(tt->eltype);
+    if (!oi || (oi->kind != K_F16 && oi->kind != K_BF16)) {
+        set_error("origin elements 0x%x are neither MSX_FLOAT16 nor MSX_BFLOAT16", ot->eltype);
+        return MPI_ERR_TYPE;
+    }
+    if (!ti || ti->kind != K_F32) {
+        set_error("target elements 0x%x are not 4-byte floats", tt->eltype);
+        return MPI_ERR_TYPE;
+    }
+    if (const int rc = elements_whole(ot, oi->size, tt, ti->size)) return rc;
+    int64_t od, td;
+    p->path = contiguous_prefix(ot, obytes, &od) && contiguous_prefix(tt, 2 * obytes, &td) ? 1 : 2;
+    return MPI_SUCCESS;
+}
+
+int dt_accw2_dev(int opidx, const Dtype* otc, const void* origin, const Dtype* ttc, void* target,
+                 const AccW2Plan& p, hipStream_t s)
+{
+    if (p.path == 0) return MPI_SUCCESS;
+    const Kind k = type_info(otc->eltype)->kind;                   // checked by the plan
+    const int64_t n = p.bytes / 2;
+    if (p.path == 1) {
+        int64_t od = 0, td = 0;
+        (void)contiguous_prefix(otc, p.bytes, &od);
+        (void)contiguous_prefix(ttc, 2 * p.bytes, &td);
+        const hipError_t e = launch_widen_combine(opidx, k, static_cast<const char*>(origin) + od,
+                                                  static_cast<char*>(target) + td, (size_t)n, s);
+        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "widening accumulate");
+    }
+    Dtype* ot = const_cast<Dtype*>(otc);
+    Dtype* tt = const_cast<Dtype*>(ttc);
+    int rc;
+    {
+        std::lock_guard<std::recursive_mutex> g(g_mu);
+        rc = build_dev_layout(ot);
+        if (rc == MPI_SUCCESS) rc = build_dev_layout(tt);
+    }
+    if (rc != MPI_SUCCESS) return rc;
+    const bool aligned = std::min<int64_t>(ot->dev.align, ptr_align(origin)) >= 2 &&
+                         std::min<int64_t>(tt->dev.align, ptr_align(target)) >= 4;
+    const hipError_t e = launch_dt_accw2(opidx, k, ot->dev, origin, tt->dev, target, n, aligned, s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout widening accumulate");
 }
 
 // ---- msx_accumulate_batch_dev: many typed combines in few launches --------------

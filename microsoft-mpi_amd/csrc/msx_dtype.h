@@ -148,6 +148,23 @@ int dt_acc2_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const D
 int dt_acc2_dev(int opidx, const Dtype* origin_t, int64_t origin_count, const void* origin,
                 const Dtype* target_t, void* target, const Acc2Plan& plan, hipStream_t s);
 
+// msx_accumulate_widen_dev (msx.h): target elem e = F_op(target elem e,
+// W(origin elem e)) over two type maps, the origin's elements MSX_FLOAT16 or
+// MSX_BFLOAT16 and the target's fp32.  dt_accw2_plan runs the call's checks
+// 4 - 6 on the host-side types (no GPU is touched; the element-type and
+// split-element rules are dt_acc2_plan's) and says what the call does;
+// dt_accw2_dev does exactly that: path 1 is the streaming kernel of
+// msx_widen.hip on the two pieces, path 2 its two-layout kernel.
+struct AccW2Plan {
+    int64_t elements = 0;   // basic elements of the origin
+    int64_t bytes = 0;      // data bytes of the origin
+    int path = 0;           // 0 nothing to do, 1 - 2 as in msx.h
+};
+int dt_accw2_plan(int opidx, const Dtype* origin_t, int64_t origin_count, const Dtype* target_t,
+                  int64_t target_count, AccW2Plan* plan);
+int dt_accw2_dev(int opidx, const Dtype* origin_t, const void* origin, const Dtype* target_t, void* target,
+                 const AccW2Plan& plan, hipStream_t s);
+
 // msx_accumulate_batch_dev (msx.h): nseg independent msx_accumulate_dev calls of
 // one builtin op in as few launches as possible.  dt_acc2_batch_plan runs the
 // call's checks 6 and 7 (dt_acc2_plan per segment in index order, then one

@@ -694,6 +694,69 @@ MSX_EXPORT int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_
     return dt_acc2_dev(r.opidx, ot, origin_count, origin, tt, target, plan, static_cast<hipStream_t>(stream));
 }
 
+// ---- msx_accumulate_widen_dev: 16-bit float origins into fp32 targets -----------
+// Checks 1 - 6 of msx.h in their order and, when they pass, the plan.  One
+// function behind the plan entry and the real call; it never touches a GPU.
+static int accumulate_widen_plan(int64_t ocount, MPI_Datatype odt, int64_t tcount, MPI_Datatype tdt, MPI_Op op,
+                                 OpRef* r, Dtype** ot, Dtype** tt, AccW2Plan* plan)
+{
+    if (ocount < 0 || tcount < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
+    const MPI_Datatype dts[2] = {odt, tdt};
+    Dtype** out[2] = {ot, tt};
+    for (int i = 0; i < 2; ++i) {
+        int rc = v_handle(dts[i], out[i]);
+        if (rc != MPI_SUCCESS) return rc;
+        if (dtype_is_derived(dts[i]) && !(*out[i])->committed) {
+            set_error("datatype 0x%x is not committed", dts[i]);
+            return MPI_ERR_TYPE;
+        }
+    }
+    int rc = v_op_handle(op, r);
+    if (rc == MPI_SUCCESS)
+        rc = v_no_sum_wide(*r, "msx_accumulate_widen_dev (the target is the fp32 accumulator: use MPI_SUM)");
+    if (rc != MPI_SUCCESS) return rc;
+    switch (r->opidx) {
+    case O_SUM: case O_PROD: case O_MAX: case O_MIN: case O_REPLACE: case O_NOOP: break;
+    case O_NULL: set_error("msx_accumulate_widen_dev takes builtin ops only"); return MPI_ERR_OP;
+    default:
+        set_error("msx_accumulate_widen_dev takes MPI_SUM, MPI_PROD, MPI_MAX, MPI_MIN, MPI_REPLACE and MPI_NO_OP, not %s",
+                  op_name(r->opidx));
+        return MPI_ERR_OP;
+    }
+    return dt_accw2_plan(r->opidx, *ot, ocount, *tt, tcount, plan);
+}
+
+MSX_EXPORT int msx_accumulate_widen_plan(int64_t origin_count, MPI_Datatype origin_type, int64_t target_count,
+                                         MPI_Datatype target_type, MPI_Op op, int64_t* elements, int* path)
+{
+    if (!elements || !path) { set_error("null plan output"); return MPI_ERR_ARG; }
+    *elements = 0;
+    *path = 0;
+    OpRef r;
+    Dtype *ot, *tt;
+    AccW2Plan plan;
+    const int rc = accumulate_widen_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
+    if (rc != MPI_SUCCESS) return rc;
+    *elements = plan.elements;
+    *path = plan.path;
+    return MPI_SUCCESS;
+}
+
+MSX_EXPORT int msx_accumulate_widen_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
+                                        void* target, int64_t target_count, MPI_Datatype target_type, MPI_Op op,
+                                        void* stream)
+{
+    OpRef r;
+    Dtype *ot, *tt;
+    AccW2Plan plan;
+    int rc = accumulate_widen_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
+    if (rc != MPI_SUCCESS || plan.path == 0) return rc;
+    if (!origin || !target) { set_error("null buffer"); return MPI_ERR_BUFFER; }
+    rc = ensure_device();
+    if (rc != MPI_SUCCESS) return rc;
+    return dt_accw2_dev(r.opidx, ot, origin, tt, target, plan, static_cast<hipStream_t>(stream));
+}
+
 // ---- msx_accumulate_batch_dev: many typed combines in few launches ---------------
 // Checks 2 - 7 of msx.h in their order (2 for the four arrays a plan takes)
 // and, when they pass, the plan.  One function behind the plan entry and the

@@ -91,6 +91,19 @@ struct Acc2Seg {
 hipError_t launch_dt_acc2_segs(int opidx, Kind k, const Acc2Seg* segs, int nseg, hipStream_t s);
 hipError_t launch_dt_copy2_segs(const Acc2Seg* segs, int nseg, hipStream_t s);
 
+// The widening accumulate (msx_widen.hip; msx.h, msx_accumulate_widen_dev):
+// inout[i] = F_op(inout[i], W(in[i])) for i in [0, count), `in` 16-bit floats
+// of kind k (K_F16 / K_BF16), `inout` fp32, launch_combine's geometry by the
+// target's size.  opidx: O_SUM, O_PROD, O_MAX, O_MIN or O_REPLACE (the
+// widening copy).  Any byte alignment of either operand.
+hipError_t launch_widen_combine(int opidx, Kind k, const void* in, void* inout, size_t count, hipStream_t s);
+// The same between two layouts: target element e (op)= W(origin element e) for
+// e < n in type-map order, 2-byte granules on the origin's map and 4-byte ones
+// on the target's.  aligned: every origin element address is a multiple of 2
+// and every target element address of 4 (layouts and pointers).
+hipError_t launch_dt_accw2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
+                           void* target, int64_t n, bool aligned, hipStream_t s);
+
 // Reference-order tree combine over p inputs (p = 1..8):
 //   out[i] = T(srcs[0][i], ..., srcs[p-1][i]) where T is the balanced binary
 //   tree of the reference's recursive-halving/doubling schedules with the

@@ -194,6 +194,8 @@ def lib():
         "msx_unpack_dev": (i, [p, i64, i, p, p]),
         "msx_accumulate_dev": (i, [p, i64, i, p, i64, i, i, p]),
         "msx_accumulate_plan": (i, [i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i), ctypes.POINTER(i)]),
+        "msx_accumulate_widen_dev": (i, [p, i64, i, p, i64, i, i, p]),
+        "msx_accumulate_widen_plan": (i, [i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i)]),
         # host arrays of device pointers / counts / datatype handles as void*
         "msx_accumulate_batch_dev": (i, [p, p, p, p, p, p, i, i, p]),
         "msx_accumulate_batch_plan": (i, [p, p, p, p, i, i, ctypes.POINTER(i), ctypes.POINTER(i64),

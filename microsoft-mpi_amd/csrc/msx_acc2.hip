@@ -26,7 +26,7 @@
 // columns of one matrix).  Each lane reads element e of both sides before it
 // stores it, and no other lane touches element e.
 //
-// acc2_elem, the serial tiles and the launch shape (make_launch2) are
+// acc2_elem, the serial tiles and the launch shape (make_launch2g) are
 // msx_acc2_dev.h's, shared with msx_acc2_segs.hip.  The whole-tile bodies stay
 // written out in the two kernels here: calling msx_acc2_dev.h's
 // acc2_tile_whole / copy2_tile_whole instead gives the same instructions in
@@ -107,7 +107,7 @@ hipError_t run_acc2(const DevLayout& Lo, const void* origin, const DevLayout& Lt
                     hipStream_t s)
 {
     Launch2 l;
-    const hipError_t e = make_launch2(Lo, origin, Lt, target, n, (int)sizeof(T), &l);
+    const hipError_t e = make_launch2g(Lo, origin, (int)sizeof(T), Lt, target, (int)sizeof(T), n, &l);
     if (e != hipSuccess) return e;
     if (align >= (int)alignof(T))
         hipLaunchKernelGGL((k_dt_acc2_tile<OP, T, true>), l.grid, dim3(64), 0, s, l.o, l.t, n, l.narrow);
@@ -121,7 +121,7 @@ hipError_t run_copy2(const DevLayout& Lo, const void* origin, const DevLayout& L
                      hipStream_t s)
 {
     Launch2 l;
-    const hipError_t e = make_launch2(Lo, origin, Lt, target, n, G, &l);
+    const hipError_t e = make_launch2g(Lo, origin, G, Lt, target, G, n, &l);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_dt_copy2_tile<G>), l.grid, dim3(64), 0, s, l.o, l.t, n, l.narrow);
     return hipGetLastError();
@@ -152,13 +152,7 @@ hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLay
     if (bytes <= 0) return hipSuccess;
     if (G < 1 || G > 16 || (G & (G - 1)) || bytes % G) return hipErrorInvalidValue;
     const int64_t n = bytes / G;
-    switch (G) {
-    case 16: return dev::run_copy2<16>(Lo, origin, Lt, target, n, s);
-    case 8: return dev::run_copy2<8>(Lo, origin, Lt, target, n, s);
-    case 4: return dev::run_copy2<4>(Lo, origin, Lt, target, n, s);
-    case 2: return dev::run_copy2<2>(Lo, origin, Lt, target, n, s);
-    default: return dev::run_copy2<1>(Lo, origin, Lt, target, n, s);
-    }
+    return for_granule(G, [&](auto g) { return dev::run_copy2<decltype(g)::value>(Lo, origin, Lt, target, n, s); });
 }
 
 }  // namespace msx

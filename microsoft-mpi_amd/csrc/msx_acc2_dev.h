@@ -7,7 +7,7 @@
 // A whole tile runs the unrolled bodies (no lane predicates); a tile cut by n,
 // and every tile of a call too large for the 32-bit divisions, runs the serial
 // loops.  The address map is msx_dtype_map.h's.  msx_acc2.hip uses acc2_elem,
-// the serial tiles and make_launch2 from here and keeps its own copy of the
+// the serial tiles and make_launch2g from here and keeps its own copy of the
 // whole-tile bodies (see its header); msx_acc2_segs.hip uses everything.
 //
 // Included by .hip units only.
@@ -124,35 +124,21 @@ struct Launch2 {
     dim3 grid;
 };
 
-inline hipError_t make_launch2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target, int64_t n,
-                               int G, Launch2* l)
-{
-    // every run offset / length must hold whole granules for the granule map
-    if (Lo.size % G || Lt.size % G || (Lo.regular && Lo.blen % G) || (Lt.regular && Lt.blen % G))
-        return hipErrorInvalidValue;
-    l->o = make_args(Lo, 1, const_cast<void*>(origin), nullptr, G);
-    l->t = make_args(Lt, 1, target, nullptr, G);
-    // the 32-bit magic divisions hold for g, and every instance, below 2^32 granules
-    l->narrow = dt_map_narrow(n, l->o.gsize, l->t.gsize);
-    const int64_t tiles = (n + 64 * kUnroll - 1) / (64 * kUnroll);
-    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
-    l->grid = dim3((unsigned)tiles);
-    return hipSuccess;
-}
-
-// make_launch2 with a granule per side: element e of the call is granule e of
-// the origin's map in Go bytes and granule e of the target's in Gt bytes (the
+// A granule per side: element e of the call is granule e of the origin's map in
+// Go bytes and granule e of the target's in Gt bytes (Go == Gt but for the
 // widening accumulate of msx_widen.hip: 2-byte elements into 4-byte ones).
 inline hipError_t make_launch2g(const DevLayout& Lo, const void* origin, int Go, const DevLayout& Lt, void* target,
                                 int Gt, int64_t n, Launch2* l)
 {
+    // every run offset / length must hold whole granules for the granule map
     if (Lo.size % Go || Lt.size % Gt || (Lo.regular && Lo.blen % Go) || (Lt.regular && Lt.blen % Gt))
         return hipErrorInvalidValue;
     l->o = make_args(Lo, 1, const_cast<void*>(origin), nullptr, Go);
     l->t = make_args(Lt, 1, target, nullptr, Gt);
+    // the 32-bit magic divisions hold for g, and every instance, below 2^32 granules
     l->narrow = dt_map_narrow(n, l->o.gsize, l->t.gsize);
     const int64_t tiles = (n + 64 * kUnroll - 1) / (64 * kUnroll);
-    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;
+    if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
     l->grid = dim3((unsigned)tiles);
     return hipSuccess;
 }

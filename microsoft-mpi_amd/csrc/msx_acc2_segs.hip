@@ -99,7 +99,7 @@ static hipError_t make_segs(const Acc2Seg* segs, int nseg, int G, Acc2Segs* c, u
         if (sg.bytes >= kAcc2SegsFuseBelow || sg.bytes % G || !sg.lo || !sg.lt || !sg.origin || !sg.target)
             return hipErrorInvalidValue;
         Launch2 l;
-        const hipError_t e = make_launch2(*sg.lo, sg.origin, *sg.lt, sg.target, sg.bytes / G, G, &l);
+        const hipError_t e = make_launch2g(*sg.lo, sg.origin, G, *sg.lt, sg.target, G, sg.bytes / G, &l);
         if (e != hipSuccess) return e;
         if (!l.narrow) return hipErrorInvalidValue;       // the caller fuses narrow segments only
         c->o[n] = l.o;
@@ -168,13 +168,7 @@ hipError_t launch_dt_copy2_segs(const Acc2Seg* segs, int nseg, hipStream_t s)
     if (nseg == 0) return hipSuccess;
     const int G = dev::min_align(segs, nseg);
     if (G < 1 || G > 16 || (G & (G - 1))) return hipErrorInvalidValue;
-    switch (G) {
-    case 16: return dev::run_copy2_segs<16>(segs, nseg, s);
-    case 8: return dev::run_copy2_segs<8>(segs, nseg, s);
-    case 4: return dev::run_copy2_segs<4>(segs, nseg, s);
-    case 2: return dev::run_copy2_segs<2>(segs, nseg, s);
-    default: return dev::run_copy2_segs<1>(segs, nseg, s);
-    }
+    return for_granule(G, [&](auto g) { return dev::run_copy2_segs<decltype(g)::value>(segs, nseg, s); });
 }
 
 }  // namespace msx

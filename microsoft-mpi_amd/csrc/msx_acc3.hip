@@ -175,7 +175,7 @@ static hipError_t make_launch3(const DevLayout& Lo, const void* origin, const De
     l->r = make_args(Lr, 1, result, nullptr, G);
     l->t = make_args(Lt, 1, target, nullptr, G);
     // the 32-bit magic divisions hold for g, and every instance, below 2^32 granules
-    l->narrow = n < 0xffffffffll && l->o.gsize < 0xffffffffll && l->r.gsize < 0xffffffffll && l->t.gsize < 0xffffffffll;
+    l->narrow = dt_map_narrow(n, l->o.gsize, l->t.gsize, l->r.gsize);
     const int64_t tiles = (n + 64 * kUnroll - 1) / (64 * kUnroll);
     if (tiles > 0x7fffffffll) return hipErrorInvalidValue;     // > 2^39 elements: beyond any HBM
     l->grid = dim3((unsigned)tiles);
@@ -236,13 +236,9 @@ hipError_t launch_dt_xchg3(const DevLayout& Lo, const void* origin, const DevLay
     if (bytes <= 0) return hipSuccess;
     if (G < 1 || G > 16 || (G & (G - 1)) || bytes % G) return hipErrorInvalidValue;
     const int64_t n = bytes / G;
-    switch (G) {
-    case 16: return dev::run_xchg3<16>(Lo, origin, Lr, result, Lt, target, n, s);
-    case 8: return dev::run_xchg3<8>(Lo, origin, Lr, result, Lt, target, n, s);
-    case 4: return dev::run_xchg3<4>(Lo, origin, Lr, result, Lt, target, n, s);
-    case 2: return dev::run_xchg3<2>(Lo, origin, Lr, result, Lt, target, n, s);
-    default: return dev::run_xchg3<1>(Lo, origin, Lr, result, Lt, target, n, s);
-    }
+    return for_granule(G, [&](auto g) {
+        return dev::run_xchg3<decltype(g)::value>(Lo, origin, Lr, result, Lt, target, n, s);
+    });
 }
 
 }  // namespace msx

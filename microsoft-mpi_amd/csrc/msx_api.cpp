@@ -22,6 +22,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 
 #include "msx_api.h"
@@ -177,9 +178,8 @@ int v_dtype_any(const void* buf, long long count, MPI_Datatype dt)
     if (count < 0) { set_error("negative count %lld", count); return MPI_ERR_COUNT; }
     if (dt == MPI_DATATYPE_NULL) { set_error("null datatype"); return MPI_ERR_TYPE; }
     if (!dtype_is_derived(dt)) return v_dtype(buf, count, dt);
-    Dtype* t = dtype_lookup(dt);
-    if (!t) { set_error("invalid datatype 0x%x", dt); return MPI_ERR_TYPE; }
-    if (!t->committed) { set_error("datatype 0x%x is not committed", dt); return MPI_ERR_TYPE; }
+    Dtype* t;
+    if (const int rc = v_committed_type(dt, &t)) return rc;
     if (buf == nullptr && t->true_lb == 0 && t->size > 0) { set_error("null buffer"); return MPI_ERR_BUFFER; }
     return MPI_SUCCESS;
 }
@@ -263,6 +263,17 @@ int v_no_sum_wide(const OpRef& r, const char* what)
     if (r.opidx != O_SUM_WIDE) return MPI_SUCCESS;
     set_error("MSX_SUM_WIDE is not defined for %s", what);
     return MPI_ERR_OP;
+}
+
+// The op of the typed accumulate family (msx_api_acc.cpp): a valid handle, not
+// MSX_SUM_WIDE (`reason` says why and what to use instead), and a builtin op.
+int v_builtin_op(MPI_Op op, const char* entry, const char* reason, OpRef* out)
+{
+    const int rc = v_op_handle(op, out);
+    if (rc != MPI_SUCCESS) return rc;
+    if (out->opidx == O_SUM_WIDE) return v_no_sum_wide(*out, (std::string(entry) + " (" + reason + ")").c_str());
+    if (out->opidx == O_NULL) { set_error("%s takes builtin ops only", entry); return MPI_ERR_OP; }
+    return MPI_SUCCESS;
 }
 
 // MpiaOpValidate (mpi_api.h:731-775), rmaOp = false

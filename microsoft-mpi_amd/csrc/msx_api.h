@@ -1,8 +1,8 @@
 // msx_api.h — what the C entry-point units share: the export macros, the
 // entry check, the error return and the argument validators.
 //
-// Internal to the entry-point units (msx_api*.cpp, msx_dtype_api.cpp,
-// msx_group.cpp); never included by a .hip unit or by the engine units.  Each
+// Internal to the entry-point units (msx_api*.cpp, msx_api_acc.cpp included,
+// msx_dtype_api.cpp, msx_group.cpp); never included by a .hip unit or by the engine units.  Each
 // function has one owner unit, named beside it.
 #pragma once
 
@@ -44,6 +44,13 @@ int v_op_handle(MPI_Op op, OpRef* out);
 int v_op(MPI_Op op, MPI_Datatype dt, OpRef* out);
 int v_no_device_op_inter(const Comm* c, const OpRef& r);
 int v_no_sum_wide(const OpRef& r, const char* what);
+// v_op_handle, v_no_sum_wide(r, "<entry> (<reason>)"), "<entry> takes builtin ops only"
+int v_builtin_op(MPI_Op op, const char* entry, const char* reason, OpRef* out);
+
+// ---- msx_dtype_api.cpp -------------------------------------------------------
+struct Dtype;
+// MpiaDatatypeValidateHandle + MpiaDatatypeValidateCommitted (mpi_api.h:53-111)
+int v_committed_type(MPI_Datatype h, Dtype** out);
 
 // The entry points of msx_dtype_api.cpp and msx_group.cpp are not traced (no
 // device work of their own except MPI_Pack / MPI_Unpack, which open their own

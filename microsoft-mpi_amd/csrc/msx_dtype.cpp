@@ -19,31 +19,12 @@
 #include <algorithm>
 #include <map>
 #include <memory>
-#include <string>
 
 #include "msx_comm.h"
 #include "msx_kernels.h"
 #include "msx_runtime.h"
 
 namespace msx {
-
-hipError_t launch_dt_copy(const DevLayout& L, int64_t count, void* typed, void* packed, bool unpack,
-                          hipStream_t s);
-hipError_t launch_dt_acc(int opidx, Kind k, const DevLayout& L, int64_t count, const void* packed,
-                         void* typed, hipStream_t s);
-// msx_acc2.hip
-hipError_t launch_dt_acc2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
-                          void* target, int64_t n, int align, hipStream_t s);
-hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target,
-                           int64_t bytes, int G, hipStream_t s);
-// msx_widen.hip (the contiguous form, launch_widen_combine, is in msx_kernels.h)
-hipError_t launch_dt_accw2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
-                           void* target, int64_t n, bool aligned, hipStream_t s);
-// msx_acc3.hip
-hipError_t launch_dt_gacc3(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lr,
-                           void* result, const DevLayout& Lt, void* target, int64_t n, int align, hipStream_t s);
-hipError_t launch_dt_xchg3(const DevLayout& Lo, const void* origin, const DevLayout& Lr, void* result,
-                           const DevLayout& Lt, void* target, int64_t bytes, int G, hipStream_t s);
 
 namespace {
 
@@ -63,7 +44,7 @@ constexpr int kPairSlots = 5;                       // direct slots 0..4: MPI_FL
 constexpr unsigned kDirectTypeBits = 0x8c000000u;   // HANDLE_TYPE_DIRECT | MPID_DATATYPE
 
 std::recursive_mutex g_mu;
-std::vector<Dtype*> g_slots;                        // derived types by direct index
+std::vector<Dtype*> g_slots;                       // derived types by direct index
 std::map<MPI_Datatype, std::unique_ptr<Dtype>> g_predef;
 
 int64_t lowbit_align(int64_t v)
@@ -185,6 +166,8 @@ void destroy(Dtype* t)
     delete t;
 }
 
+}  // namespace
+
 // The single run of a one-run type (either form).
 bool single_run(const Dtype* t, DtRun* r)
 {
@@ -192,6 +175,8 @@ bool single_run(const Dtype* t, DtRun* r)
     if (t->rn == 0 && t->runs.size() == 1) { *r = t->runs[0]; return true; }
     return false;
 }
+
+namespace {
 
 void copy_layout(Dtype* t, const Dtype* o)
 {
@@ -938,8 +923,6 @@ int dtype_free(MPI_Datatype* h)
 // ---------------------------------------------------------------------------
 // device layout
 // ---------------------------------------------------------------------------
-namespace {
-
 // DevLayout::align of a type, from the host form alone (no device layout needed).
 int layout_align(const Dtype* t)
 {
@@ -956,6 +939,10 @@ int layout_align(const Dtype* t)
     }
     return (int)al;
 }
+
+int64_t ptr_align(const void* p) { return lowbit_align((int64_t)(uintptr_t)p); }
+
+namespace {
 
 int build_dev_layout(Dtype* t)
 {
@@ -1015,8 +1002,6 @@ int build_dev_layout(Dtype* t)
     t->dev_ready = true;
     return MPI_SUCCESS;
 }
-
-int64_t ptr_align(const void* p) { return lowbit_align((int64_t)(uintptr_t)p); }
 
 // Device scratch for staging host operands (grows; guarded by its own lock).
 std::mutex g_stage_mu;
@@ -1144,73 +1129,6 @@ void dt_span(const Dtype* t, int64_t count, int64_t* lo, int64_t* hi)
     *hi = rh + std::max<int64_t>(0, shift);
 }
 
-int dt_pack_dev(const Dtype* tc, int64_t count, const void* typed, void* packed, hipStream_t s)
-{
-    if (count <= 0 || tc->size == 0) return MPI_SUCCESS;
-    Dtype* t = const_cast<Dtype*>(tc);
-    int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        rc = build_dev_layout(t);
-    }
-    if (rc != MPI_SUCCESS) return rc;
-    DevLayout L = t->dev;
-    L.align = (int)std::min<int64_t>({(int64_t)L.align, ptr_align(typed), ptr_align(packed)});
-    hipError_t e = launch_dt_copy(L, count, const_cast<void*>(typed), packed, false, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "datatype pack");
-}
-
-int dt_unpack_dev(const Dtype* tc, int64_t count, const void* packed, void* typed, hipStream_t s)
-{
-    if (count <= 0 || tc->size == 0) return MPI_SUCCESS;
-    Dtype* t = const_cast<Dtype*>(tc);
-    int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        rc = build_dev_layout(t);
-    }
-    if (rc != MPI_SUCCESS) return rc;
-    DevLayout L = t->dev;
-    L.align = (int)std::min<int64_t>({(int64_t)L.align, ptr_align(typed), ptr_align(packed)});
-    hipError_t e = launch_dt_copy(L, count, typed, const_cast<void*>(packed), true, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "datatype unpack");
-}
-
-int dt_acc_dev(int opidx, const Dtype* tc, int64_t count, const void* packed, void* typed, hipStream_t s)
-{
-    if (count <= 0 || tc->size == 0 || opidx == O_NOOP) return MPI_SUCCESS;
-    if (opidx == O_REPLACE) return dt_unpack_dev(tc, count, packed, typed, s);
-    // the reference applies the op with dtp->eltype (packethandling.cpp:2993-3001):
-    // a mixed type (eltype NULL) or an illegal pair only sets op_errno
-    const TypeInfo* ti = type_info(tc->eltype);
-    if (!ti || op_check_dtype(opidx, tc->eltype) != MPI_SUCCESS) return MPI_SUCCESS;
-    // every run holds whole elements (true for any type built from one basic type)
-    if (tc->rn && tc->rlen % ti->size) {
-        set_error("datatype runs split elements of 0x%x", tc->eltype);
-        return MPI_ERR_TYPE;
-    }
-    for (const DtRun& r : tc->runs)
-        if (r.len % ti->size) {
-            set_error("datatype runs split elements of 0x%x", tc->eltype);
-            return MPI_ERR_TYPE;
-        }
-    Dtype* t = const_cast<Dtype*>(tc);
-    int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        rc = build_dev_layout(t);
-    }
-    if (rc != MPI_SUCCESS) return rc;
-    DevLayout L = t->dev;
-    L.align = (int)std::min<int64_t>({(int64_t)L.align, ptr_align(typed), ptr_align(packed)});
-    hipError_t e = launch_dt_acc(opidx, ti->kind, L, count, packed, typed, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "datatype accumulate");
-}
-
-namespace {
-
-// Every run of `t` holds whole elements of `esz` bytes (true for any type built
-// from one basic type whose data bytes are its extent).
 bool runs_hold_elements(const Dtype* t, int64_t esz)
 {
     if (t->rn && t->rlen % esz) return false;
@@ -1219,399 +1137,66 @@ bool runs_hold_elements(const Dtype* t, int64_t esz)
     return true;
 }
 
-// The first `bytes` (> 0) data bytes of the type's instances lie in one piece
-// at *disp: inside the first run, or over one-run instances that touch.
-bool contiguous_prefix(const Dtype* t, int64_t bytes, int64_t* disp)
+// The one place that builds device layouts (msx_dtype.h).
+int dev_sides(DevSide* side, int n)
 {
-    const DtRun first = t->rn ? DtRun{t->rfirst, t->rlen} : t->runs[0];
-    DtRun r{0, 0};
-    *disp = first.disp;
-    return bytes <= first.len || (single_run(t, &r) && t->size == t->extent);
-}
-
-// Check 6's rule that both types have one basic element type (a mixed struct
-// and the pair types have none), for dt_acc2_plan and dt_accw2_plan.
-int single_element_types(const Dtype* ot, const Dtype* tt)
-{
-    if (ot->eltype != MPI_DATATYPE_NULL && tt->eltype != MPI_DATATYPE_NULL) return MPI_SUCCESS;
-    set_error("%s datatype has no single basic element type", ot->eltype == MPI_DATATYPE_NULL ? "origin" : "target");
-    return MPI_ERR_TYPE;
-}
-
-// Check 6's rule that neither type map splits an element (osz / tsz bytes).
-int elements_whole(const Dtype* ot, int64_t osz, const Dtype* tt, int64_t tsz)
-{
-    if (runs_hold_elements(ot, osz) && runs_hold_elements(tt, tsz)) return MPI_SUCCESS;
-    set_error("datatype runs split elements of 0x%x", tt->eltype);
-    return MPI_ERR_TYPE;
-}
-
-}  // namespace
-
-// Checks 4 - 6 of msx_accumulate_dev (msx.h) and the path the call takes: a pure
-// function of the two host-side types, the counts and the op.
-int dt_acc2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, int64_t tcount, Acc2Plan* p)
-{
-    *p = Acc2Plan();
-    const int64_t lim = (int64_t)1 << 62;
-    if ((ot->size > 0 && ocount > lim / ot->size) || (tt->size > 0 && tcount > lim / tt->size)) {
-        set_error("count overflows the data size");
-        return MPI_ERR_COUNT;
+    std::lock_guard<std::recursive_mutex> g(g_mu);
+    for (int i = 0; i < n; ++i) {
+        Dtype* t = const_cast<Dtype*>(side[i].type);
+        const int rc = build_dev_layout(t);
+        if (rc != MPI_SUCCESS) return rc;
+        side[i].L = &t->dev;
+        side[i].align = (int)std::min<int64_t>(t->dev.align, ptr_align(side[i].ptr));
     }
-    const int64_t obytes = ocount * ot->size, tbytes = tcount * tt->size;
-    if (obytes > tbytes) {
-        set_error("accumulate truncated: %lld origin bytes into %lld", (long long)obytes, (long long)tbytes);
-        return MPI_ERR_TRUNCATE;
-    }
-    // n_elements also counts the MPI_LB / MPI_UB markers of a struct (a subarray has two)
-    p->elements = ot->el_size > 0 ? obytes / ot->el_size : ocount * ot->n_elements;
-    p->bytes = obytes;
-    if (obytes == 0 || opidx == O_NOOP) return MPI_SUCCESS;
-    if (opidx == O_REPLACE) {
-        p->granule = std::min(layout_align(ot), layout_align(tt));
-    } else {
-        const TypeInfo* oi = type_info(ot->eltype);
-        const TypeInfo* ti = type_info(tt->eltype);
-        if (const int rc = single_element_types(ot, tt)) return rc;
-        if ((oi ? oi->kind : K_NONE) != (ti ? ti->kind : K_NONE)) {
-            set_error("origin elements 0x%x and target elements 0x%x differ in kind", ot->eltype, tt->eltype);
-            return MPI_ERR_TYPE;
-        }
-        for (MPI_Datatype el : {ot->eltype, tt->eltype})
-            if (!type_info(el) || op_check_dtype(opidx, el) != MPI_SUCCESS) {
-                set_error("%s is not defined for datatype 0x%x", op_name(opidx), el);
-                return MPI_ERR_OP;
-            }
-        if (const int rc = elements_whole(ot, oi->size, tt, ti->size)) return rc;
-        p->granule = ti->size;
-    }
-    int64_t od, td;
-    const bool oc = contiguous_prefix(ot, obytes, &od), tc = contiguous_prefix(tt, obytes, &td);
-    if (oc && tc) p->path = 1;
-    else if (oc && obytes % tt->size == 0) p->path = 2;      // dt_acc_dev covers whole target instances
-    else if (tc && opidx == O_REPLACE) p->path = 3;
-    else p->path = 4;
     return MPI_SUCCESS;
 }
 
-int dt_acc2_dev(int opidx, const Dtype* otc, int64_t ocount, const void* origin, const Dtype* ttc, void* target,
-                const Acc2Plan& p, hipStream_t s)
+// The one-layout launches' prologue: t's layout, its align lowered by both addresses.
+static int packed_layout(const Dtype* t, const void* typed, const void* packed, DevLayout* L)
 {
-    if (p.path == 0) return MPI_SUCCESS;
-    int64_t od = 0, td = 0;
-    (void)contiguous_prefix(otc, p.bytes, &od);
-    (void)contiguous_prefix(ttc, p.bytes, &td);
-    const char* src = static_cast<const char*>(origin) + od;      // paths 1, 2: the origin's one piece
-    char* dst = static_cast<char*>(target) + td;                  // paths 1, 3: the target's
-    const TypeInfo* ti = type_info(ttc->eltype);                  // an op's element (checked by the plan)
-    switch (p.path) {
-    case 1: {
-        if (opidx != O_REPLACE) return reduce_local_device(opidx, ti->kind, src, dst, (size_t)(p.bytes / ti->size), s);
-        const void* ps = src;
-        void* pd = dst;
-        const size_t nb = (size_t)p.bytes;
-        const hipError_t e = launch_copy_segs(&ps, &pd, &nb, 1, s);
-        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "copy kernel launch");
-    }
-    case 2:
-        return dt_acc_dev(opidx, ttc, p.bytes / ttc->size, src, target, s);
-    case 3:
-        return dt_pack_dev(otc, ocount, origin, dst, s);
-    default:
-        break;
-    }
-    Dtype* ot = const_cast<Dtype*>(otc);
-    Dtype* tt = const_cast<Dtype*>(ttc);
-    int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        rc = build_dev_layout(ot);
-        if (rc == MPI_SUCCESS) rc = build_dev_layout(tt);
-    }
+    DevSide sd{t, typed};
+    const int rc = dev_sides(&sd, 1);
     if (rc != MPI_SUCCESS) return rc;
-    const int align = (int)std::min<int64_t>({(int64_t)ot->dev.align, (int64_t)tt->dev.align, ptr_align(origin),
-                                              ptr_align(target)});
-    const hipError_t e = opidx == O_REPLACE
-                             ? launch_dt_copy2(ot->dev, origin, tt->dev, target, p.bytes, align, s)
-                             : launch_dt_acc2(opidx, ti->kind, ot->dev, origin, tt->dev, target, p.bytes / ti->size,
-                                              align, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout datatype accumulate");
+    *L = *sd.L;
+    L->align = (int)std::min<int64_t>(sd.align, ptr_align(packed));
+    return MPI_SUCCESS;
 }
 
-// ---- msx_accumulate_widen_dev: 16-bit float origins into fp32 targets ------------
-// Checks 4 - 6 of msx_accumulate_widen_dev (msx.h) and the path the call takes: a
-// pure function of the two host-side types, the counts and the op.
-int dt_accw2_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* tt, int64_t tcount, AccW2Plan* p)
+static int dt_copy_dev(const Dtype* t, int64_t count, const void* typed, const void* packed, bool unpack, hipStream_t s)
 {
-    *p = AccW2Plan();
-    const int64_t lim = (int64_t)1 << 62;
-    if ((ot->size > 0 && ocount > lim / ot->size) || (tt->size > 0 && tcount > lim / tt->size)) {
-        set_error("count overflows the data size");
-        return MPI_ERR_COUNT;
-    }
-    const int64_t obytes = ocount * ot->size, tbytes = tcount * tt->size;
-    if (obytes > tbytes / 2) {      // 2 * obytes > tbytes
-        set_error("widening accumulate truncated: %lld origin bytes (twice that widened) into %lld",
-                  (long long)obytes, (long long)tbytes);
-        return MPI_ERR_TRUNCATE;
-    }
-    p->elements = ot->el_size > 0 ? obytes / ot->el_size : ocount * ot->n_elements;
-    p->bytes = obytes;
-    if (obytes == 0 || opidx == O_NOOP) return MPI_SUCCESS;
-    if (const int rc = single_element_types(ot, tt)) return rc;
-    const TypeInfo* oi = type_info(ot->eltype);
-    const TypeInfo* ti = type_info(tt->eltype);
-    if (!oi || (oi->kind != K_F16 && oi->kind != K_BF16)) {
-        set_error("origin elements 0x%x are neither MSX_FLOAT16 nor MSX_BFLOAT16", ot->eltype);
+    if (count <= 0 || t->size == 0) return MPI_SUCCESS;
+    DevLayout L;
+    if (const int rc = packed_layout(t, typed, packed, &L)) return rc;
+    hipError_t e = launch_dt_copy(L, count, const_cast<void*>(typed), const_cast<void*>(packed), unpack, s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, unpack ? "datatype unpack" : "datatype pack");
+}
+
+int dt_pack_dev(const Dtype* t, int64_t count, const void* typed, void* packed, hipStream_t s)
+{
+    return dt_copy_dev(t, count, typed, packed, false, s);
+}
+
+int dt_unpack_dev(const Dtype* t, int64_t count, const void* packed, void* typed, hipStream_t s)
+{
+    return dt_copy_dev(t, count, typed, packed, true, s);
+}
+
+int dt_acc_dev(int opidx, const Dtype* t, int64_t count, const void* packed, void* typed, hipStream_t s)
+{
+    if (count <= 0 || t->size == 0 || opidx == O_NOOP) return MPI_SUCCESS;
+    if (opidx == O_REPLACE) return dt_unpack_dev(t, count, packed, typed, s);
+    // the reference applies the op with dtp->eltype (packethandling.cpp:2993-3001):
+    // a mixed type (eltype NULL) or an illegal pair only sets op_errno
+    const TypeInfo* ti = type_info(t->eltype);
+    if (!ti || op_check_dtype(opidx, t->eltype) != MPI_SUCCESS) return MPI_SUCCESS;
+    if (!runs_hold_elements(t, ti->size)) {
+        set_error("datatype runs split elements of 0x%x", t->eltype);
         return MPI_ERR_TYPE;
     }
-    if (!ti || ti->kind != K_F32) {
-        set_error("target elements 0x%x are not 4-byte floats", tt->eltype);
-        return MPI_ERR_TYPE;
-    }
-    if (const int rc = elements_whole(ot, oi->size, tt, ti->size)) return rc;
-    int64_t od, td;
-    p->path = contiguous_prefix(ot, obytes, &od) && contiguous_prefix(tt, 2 * obytes, &td) ? 1 : 2;
-    return MPI_SUCCESS;
-}
-
-int dt_accw2_dev(int opidx, const Dtype* otc, const void* origin, const Dtype* ttc, void* target,
-                 const AccW2Plan& p, hipStream_t s)
-{
-    if (p.path == 0) return MPI_SUCCESS;
-    const Kind k = type_info(otc->eltype)->kind;                   // checked by the plan
-    const int64_t n = p.bytes / 2;
-    if (p.path == 1) {
-        int64_t od = 0, td = 0;
-        (void)contiguous_prefix(otc, p.bytes, &od);
-        (void)contiguous_prefix(ttc, 2 * p.bytes, &td);
-        const hipError_t e = launch_widen_combine(opidx, k, static_cast<const char*>(origin) + od,
-                                                  static_cast<char*>(target) + td, (size_t)n, s);
-        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "widening accumulate");
-    }
-    Dtype* ot = const_cast<Dtype*>(otc);
-    Dtype* tt = const_cast<Dtype*>(ttc);
-    int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        rc = build_dev_layout(ot);
-        if (rc == MPI_SUCCESS) rc = build_dev_layout(tt);
-    }
-    if (rc != MPI_SUCCESS) return rc;
-    const bool aligned = std::min<int64_t>(ot->dev.align, ptr_align(origin)) >= 2 &&
-                         std::min<int64_t>(tt->dev.align, ptr_align(target)) >= 4;
-    const hipError_t e = launch_dt_accw2(opidx, k, ot->dev, origin, tt->dev, target, n, aligned, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "two-layout widening accumulate");
-}
-
-// ---- msx_accumulate_batch_dev: many typed combines in few launches --------------
-int acc2_batch_width() { return kAcc2SegsWidth; }
-int64_t acc2_batch_fuse_below() { return kAcc2SegsFuseBelow; }
-int Acc2BatchPlan::launches() const { return (fused + kAcc2SegsWidth - 1) / kAcc2SegsWidth + single; }
-
-// Checks 6 and 7 of msx_accumulate_batch_dev (msx.h) and what the call does with
-// each non-empty segment: a pure function of the host-side types, the counts
-// and the op.
-int dt_acc2_batch_plan(int opidx, const Dtype* const* ot, const int64_t* ocount, const Dtype* const* tt,
-                       const int64_t* tcount, int nseg, Acc2BatchPlan* plan)
-{
-    *plan = Acc2BatchPlan();
-    for (int i = 0; i < nseg; ++i) {
-        Acc2BatchStep st;
-        const int rc = dt_acc2_plan(opidx, ot[i], ocount[i], tt[i], tcount[i], &st.plan);
-        if (rc != MPI_SUCCESS) {
-            const std::string why = last_error();
-            set_error("segment %d: %s", i, why.c_str());
-            return rc;
-        }
-        if (st.plan.path == 0) continue;      // no origin data bytes, or MPI_NO_OP
-        st.seg = i;
-        st.ot = ot[i];
-        st.tt = tt[i];
-        st.ocount = ocount[i];
-        // The fused kernels divide in 32 bits.  The granule is at least one
-        // byte (MPI_REPLACE's depends on the pointers, which a plan does not
-        // see), so sizes in bytes bound the sizes in granules.
-        st.fused = st.plan.bytes < kAcc2SegsFuseBelow && dt_map_narrow(st.plan.bytes, ot[i]->size, tt[i]->size);
-        plan->steps.push_back(st);
-    }
-    if (opidx != O_REPLACE)
-        for (const Acc2BatchStep& st : plan->steps) {
-            const Acc2BatchStep& s0 = plan->steps[0];
-            if (type_info(st.tt->eltype)->kind != type_info(s0.tt->eltype)->kind) {
-                set_error("segment %d has elements 0x%x and segment %d elements 0x%x: one element kind per call",
-                          s0.seg, s0.tt->eltype, st.seg, st.tt->eltype);
-                return MPI_ERR_TYPE;
-            }
-        }
-    for (const Acc2BatchStep& st : plan->steps) ++(st.fused ? plan->fused : plan->single);
-    return MPI_SUCCESS;
-}
-
-int dt_acc2_batch_dev(int opidx, const Acc2BatchPlan& plan, const void* const* origin, void* const* target,
-                      hipStream_t s)
-{
-    if (plan.steps.empty()) return MPI_SUCCESS;
-    // every fused segment's device layout before the first launch (a single
-    // segment builds its own in dt_acc2_dev)
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        for (const Acc2BatchStep& st : plan.steps) {
-            if (!st.fused) continue;
-            int rc = build_dev_layout(const_cast<Dtype*>(st.ot));
-            if (rc == MPI_SUCCESS) rc = build_dev_layout(const_cast<Dtype*>(st.tt));
-            if (rc != MPI_SUCCESS) return rc;
-        }
-    }
-    const Kind k = opidx == O_REPLACE ? K_NONE : type_info(plan.steps[0].tt->eltype)->kind;
-    Acc2Seg segs[kAcc2SegsWidth];
-    int n = 0, left = plan.fused;
-    for (const Acc2BatchStep& st : plan.steps) {
-        const int i = st.seg;
-        if (!st.fused) {
-            const int rc = dt_acc2_dev(opidx, st.ot, st.ocount, origin[i], st.tt, target[i], st.plan, s);
-            if (rc != MPI_SUCCESS) return rc;
-            continue;
-        }
-        // dt_acc2_dev's alignment: both layouts and both pointers
-        const int align = (int)std::min<int64_t>({(int64_t)st.ot->dev.align, (int64_t)st.tt->dev.align,
-                                                  ptr_align(origin[i]), ptr_align(target[i])});
-        segs[n++] = Acc2Seg{&st.ot->dev, origin[i], &st.tt->dev, target[i], st.plan.bytes, align};
-        if (n == kAcc2SegsWidth || n == left) {
-            const hipError_t e = opidx == O_REPLACE ? launch_dt_copy2_segs(segs, n, s)
-                                                    : launch_dt_acc2_segs(opidx, k, segs, n, s);
-            if (e != hipSuccess) return hip_fail(e, "batched two-layout datatype accumulate");
-            left -= n;
-            n = 0;
-        }
-    }
-    return MPI_SUCCESS;
-}
-
-// Checks 4 - 6 of msx_get_accumulate_dev (msx.h) and the path the call takes: a
-// pure function of the host-side types, the counts and the op.  `ot` is null
-// under MPI_NO_OP, where the result triple counts the elements.
-int dt_gacc3_plan(int opidx, const Dtype* ot, int64_t ocount, const Dtype* rt, int64_t rcount, const Dtype* tt,
-                  int64_t tcount, Acc3Plan* p)
-{
-    *p = Acc3Plan();
-    const int64_t lim = (int64_t)1 << 62;
-    for (const auto& tc : {std::make_pair(ot, ocount), std::make_pair(rt, rcount), std::make_pair(tt, tcount)})
-        if (tc.first && tc.first->size > 0 && tc.second > lim / tc.first->size) {
-            set_error("count overflows the data size");
-            return MPI_ERR_COUNT;
-        }
-    const Dtype* nt = ot ? ot : rt;                      // the triple that counts the elements
-    const int64_t nbytes = (ot ? ocount : rcount) * nt->size;
-    const int64_t rbytes = rcount * rt->size, tbytes = tcount * tt->size;
-    if (nbytes > tbytes) {
-        set_error("accumulate truncated: %lld origin bytes into %lld", (long long)nbytes, (long long)tbytes);
-        return MPI_ERR_TRUNCATE;
-    }
-    if (nbytes > rbytes) {
-        set_error("get_accumulate truncated: %lld target bytes into %lld of the result", (long long)nbytes,
-                  (long long)rbytes);
-        return MPI_ERR_TRUNCATE;
-    }
-    p->elements = nt->el_size > 0 ? nbytes / nt->el_size : (ot ? ocount : rcount) * nt->n_elements;
-    p->bytes = nbytes;
-    if (nbytes == 0) return MPI_SUCCESS;
-    if (opidx == O_NOOP) {
-        p->granule = std::min(layout_align(rt), layout_align(tt));
-    } else if (opidx == O_REPLACE) {
-        p->granule = std::min({layout_align(ot), layout_align(rt), layout_align(tt)});
-    } else {
-        const Dtype* side[3] = {ot, rt, tt};
-        const char* name[3] = {"origin", "result", "target"};
-        for (int i = 0; i < 3; ++i)
-            if (side[i]->eltype == MPI_DATATYPE_NULL) {
-                set_error("%s datatype has no single basic element type", name[i]);
-                return MPI_ERR_TYPE;
-            }
-        const TypeInfo* ti = type_info(tt->eltype);
-        for (int i = 0; i < 2; ++i) {
-            const TypeInfo* xi = type_info(side[i]->eltype);
-            if ((xi ? xi->kind : K_NONE) != (ti ? ti->kind : K_NONE)) {
-                set_error("%s elements 0x%x and target elements 0x%x differ in kind", name[i], side[i]->eltype,
-                          tt->eltype);
-                return MPI_ERR_TYPE;
-            }
-        }
-        for (const Dtype* x : side)
-            if (!type_info(x->eltype) || op_check_dtype(opidx, x->eltype) != MPI_SUCCESS) {
-                set_error("%s is not defined for datatype 0x%x", op_name(opidx), x->eltype);
-                return MPI_ERR_OP;
-            }
-        for (const Dtype* x : side)
-            if (!runs_hold_elements(x, ti->size)) {
-                set_error("datatype runs split elements of 0x%x", x->eltype);
-                return MPI_ERR_TYPE;
-            }
-        p->granule = ti->size;
-    }
-    int64_t d;
-    const bool oc = !ot || contiguous_prefix(ot, nbytes, &d);
-    const bool all = oc && contiguous_prefix(rt, nbytes, &d) && contiguous_prefix(tt, nbytes, &d);
-    p->path = all ? 1 : (opidx == O_NOOP ? 2 : 3);
-    return MPI_SUCCESS;
-}
-
-int dt_gacc3_dev(int opidx, const Dtype* otc, const void* origin, const Dtype* rtc, int64_t rcount, void* result,
-                 const Dtype* ttc, void* target, const Acc3Plan& p, hipStream_t s)
-{
-    if (p.path == 0) return MPI_SUCCESS;
-    if (p.path == 1) {
-        int64_t od = 0, rd = 0, td = 0;
-        if (otc) (void)contiguous_prefix(otc, p.bytes, &od);
-        (void)contiguous_prefix(rtc, p.bytes, &rd);
-        (void)contiguous_prefix(ttc, p.bytes, &td);
-        char* res = static_cast<char*>(result) + rd;
-        char* dst = static_cast<char*>(target) + td;
-        hipError_t e;
-        if (opidx == O_NOOP) {
-            const void* ps = dst;
-            void* pd = res;
-            const size_t nb = (size_t)p.bytes;
-            e = launch_copy_segs(&ps, &pd, &nb, 1, s);
-        } else {
-            const char* src = static_cast<const char*>(origin) + od;
-            const TypeInfo* ti = type_info(ttc->eltype);      // an op's element (checked by the plan)
-            e = opidx == O_REPLACE ? launch_fetch_combine(opidx, K_U8, src, res, dst, (size_t)p.bytes, s)
-                                   : launch_fetch_combine(opidx, ti->kind, src, res, dst, (size_t)(p.bytes / ti->size), s);
-        }
-        return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "fetch-and-combine kernel launch");
-    }
-    if (p.path == 2) {
-        // MPI_NO_OP: the typed -> typed copy target -> result.  Over whole target
-        // instances it is msx_accumulate_dev's plan; a prefix that ends inside
-        // an instance is what only the two-layout kernel covers.
-        Acc2Plan q;
-        if (p.bytes % ttc->size == 0) {
-            const int rc = dt_acc2_plan(O_REPLACE, ttc, p.bytes / ttc->size, rtc, rcount, &q);
-            if (rc != MPI_SUCCESS) return rc;
-        } else {
-            q.bytes = p.bytes;
-            q.path = 4;
-        }
-        return dt_acc2_dev(O_REPLACE, ttc, p.bytes / ttc->size, target, rtc, result, q, s);
-    }
-    Dtype* lay[3] = {const_cast<Dtype*>(otc), const_cast<Dtype*>(rtc), const_cast<Dtype*>(ttc)};
-    int rc = MPI_SUCCESS;
-    {
-        std::lock_guard<std::recursive_mutex> g(g_mu);
-        for (int i = 0; i < 3 && rc == MPI_SUCCESS; ++i) rc = build_dev_layout(lay[i]);
-    }
-    if (rc != MPI_SUCCESS) return rc;
-    const int align = (int)std::min<int64_t>({(int64_t)lay[0]->dev.align, (int64_t)lay[1]->dev.align,
-                                              (int64_t)lay[2]->dev.align, ptr_align(origin), ptr_align(result),
-                                              ptr_align(target)});
-    const TypeInfo* ti = type_info(ttc->eltype);
-    const hipError_t e =
-        opidx == O_REPLACE
-            ? launch_dt_xchg3(lay[0]->dev, origin, lay[1]->dev, result, lay[2]->dev, target, p.bytes, align, s)
-            : launch_dt_gacc3(opidx, ti->kind, lay[0]->dev, origin, lay[1]->dev, result, lay[2]->dev, target,
-                              p.bytes / ti->size, align, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "three-layout datatype get-accumulate");
+    DevLayout L;
+    if (const int rc = packed_layout(t, typed, packed, &L)) return rc;
+    hipError_t e = launch_dt_acc(opidx, ti->kind, L, count, packed, typed, s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_fail(e, "datatype accumulate");
 }
 
 int dt_pack_any(const Dtype* t, int64_t count, const void* typed, void* packed)

@@ -11,10 +11,6 @@
 #include <limits.h>
 #include <string.h>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
 #include "../../include/mpi.h"
 #include "msx_api.h"
 #include "msx_comm.h"
@@ -48,6 +44,18 @@ int v_handle(MPI_Datatype h, Dtype** out)
     return MPI_SUCCESS;
 }
 
+}  // namespace
+
+int msx::v_committed_type(MPI_Datatype h, Dtype** out)
+{
+    const int rc = v_handle(h, out);
+    if (rc != MPI_SUCCESS) return rc;
+    if (dtype_is_derived(h) && !(*out)->committed) { set_error("datatype 0x%x is not committed", h); return MPI_ERR_TYPE; }
+    return MPI_SUCCESS;
+}
+
+namespace {
+
 // MpiaDatatypeValidateNotPermanent (mpi_api.h:166-185)
 int v_not_permanent(MPI_Datatype h)
 {
@@ -61,10 +69,9 @@ int v_typed(const void* buf, int count, MPI_Datatype h, Dtype** out)
     *out = nullptr;
     if (count == 0) return MPI_SUCCESS;
     if (count < 0) { set_error("negative count %d", count); return MPI_ERR_COUNT; }
-    int rc = v_handle(h, out);
+    int rc = v_committed_type(h, out);
     if (rc != MPI_SUCCESS) return rc;
     if (dtype_is_derived(h)) {
-        if (!(*out)->committed) { set_error("datatype 0x%x is not committed", h); return MPI_ERR_TYPE; }
         if (buf == nullptr && (*out)->true_lb == 0 && (*out)->size > 0) { set_error("null buffer"); return MPI_ERR_BUFFER; }
     } else if (buf == nullptr) {
         set_error("null buffer");
@@ -595,11 +602,7 @@ MSX_EXPORT int MPI_Pack_size(int incount, MPI_Datatype datatype, MPI_Comm comm, 
     api_require_init("MPI_Pack_size");
     int rc = api_comm_valid(comm);
     Dtype* t = nullptr;
-    if (rc == MPI_SUCCESS) rc = v_handle(datatype, &t);
-    if (rc == MPI_SUCCESS && dtype_is_derived(datatype) && !t->committed) {
-        set_error("datatype 0x%x is not committed", datatype);
-        rc = MPI_ERR_TYPE;
-    }
+    if (rc == MPI_SUCCESS) rc = v_committed_type(datatype, &t);
     if (rc == MPI_SUCCESS && incount < 0) { set_error("negative count %d", incount); rc = MPI_ERR_COUNT; }
     if (rc == MPI_SUCCESS && !size) rc = arg_err("null size");
     if (rc != MPI_SUCCESS) return fail("MPI_Pack_size", rc);
@@ -614,11 +617,7 @@ MSX_EXPORT int MPI_Pack_size(int incount, MPI_Datatype datatype, MPI_Comm comm, 
 static int dev_typed_check(int64_t count, MPI_Datatype dt, Dtype** t)
 {
     if (count < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
-    int rc = v_handle(dt, t);
-    if (rc == MPI_SUCCESS && dtype_is_derived(dt) && !(*t)->committed) {
-        set_error("datatype 0x%x is not committed", dt);
-        rc = MPI_ERR_TYPE;
-    }
+    int rc = v_committed_type(dt, t);
     if (rc == MPI_SUCCESS) rc = ensure_device();
     return rc;
 }
@@ -637,277 +636,6 @@ MSX_EXPORT int msx_unpack_dev(const void* packed, int64_t count, MPI_Datatype da
     int rc = dev_typed_check(count, datatype, &t);
     if (rc != MPI_SUCCESS || count == 0) return rc;
     return dt_unpack_dev(t, count, packed, typed, static_cast<hipStream_t>(stream));
-}
-
-// ---- msx_accumulate_dev: a combine between two datatype layouts ----------------
-// Checks 1 - 6 of msx.h in their order and, when they pass, the plan.  One
-// function behind the plan entry and the real call; it never touches a GPU.
-static int accumulate_plan(int64_t ocount, MPI_Datatype odt, int64_t tcount, MPI_Datatype tdt, MPI_Op op, OpRef* r,
-                           Dtype** ot, Dtype** tt, Acc2Plan* plan)
-{
-    if (ocount < 0 || tcount < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
-    const MPI_Datatype dts[2] = {odt, tdt};
-    Dtype** out[2] = {ot, tt};
-    for (int i = 0; i < 2; ++i) {
-        int rc = v_handle(dts[i], out[i]);
-        if (rc != MPI_SUCCESS) return rc;
-        if (dtype_is_derived(dts[i]) && !(*out[i])->committed) {
-            set_error("datatype 0x%x is not committed", dts[i]);
-            return MPI_ERR_TYPE;
-        }
-    }
-    int rc = v_op_handle(op, r);
-    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(*r, "msx_accumulate_dev (one combine per element: use MPI_SUM)");
-    if (rc != MPI_SUCCESS) return rc;
-    if (r->opidx == O_NULL) { set_error("msx_accumulate_dev takes builtin ops only"); return MPI_ERR_OP; }
-    return dt_acc2_plan(r->opidx, *ot, ocount, *tt, tcount, plan);
-}
-
-MSX_EXPORT int msx_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type, int64_t target_count,
-                                   MPI_Datatype target_type, MPI_Op op, int64_t* elements, int* path, int* granule)
-{
-    if (!elements || !path || !granule) { set_error("null plan output"); return MPI_ERR_ARG; }
-    *elements = 0;
-    *path = *granule = 0;
-    OpRef r;
-    Dtype *ot, *tt;
-    Acc2Plan plan;
-    const int rc = accumulate_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
-    if (rc != MPI_SUCCESS) return rc;
-    *elements = plan.elements;
-    *path = plan.path;
-    *granule = plan.path ? plan.granule : 0;
-    return MPI_SUCCESS;
-}
-
-MSX_EXPORT int msx_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type, void* target,
-                                  int64_t target_count, MPI_Datatype target_type, MPI_Op op, void* stream)
-{
-    OpRef r;
-    Dtype *ot, *tt;
-    Acc2Plan plan;
-    int rc = accumulate_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
-    if (rc != MPI_SUCCESS || plan.path == 0) return rc;
-    if (!origin || !target) { set_error("null buffer"); return MPI_ERR_BUFFER; }
-    rc = ensure_device();
-    if (rc != MPI_SUCCESS) return rc;
-    return dt_acc2_dev(r.opidx, ot, origin_count, origin, tt, target, plan, static_cast<hipStream_t>(stream));
-}
-
-// ---- msx_accumulate_widen_dev: 16-bit float origins into fp32 targets -----------
-// Checks 1 - 6 of msx.h in their order and, when they pass, the plan.  One
-// function behind the plan entry and the real call; it never touches a GPU.
-static int accumulate_widen_plan(int64_t ocount, MPI_Datatype odt, int64_t tcount, MPI_Datatype tdt, MPI_Op op,
-                                 OpRef* r, Dtype** ot, Dtype** tt, AccW2Plan* plan)
-{
-    if (ocount < 0 || tcount < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
-    const MPI_Datatype dts[2] = {odt, tdt};
-    Dtype** out[2] = {ot, tt};
-    for (int i = 0; i < 2; ++i) {
-        int rc = v_handle(dts[i], out[i]);
-        if (rc != MPI_SUCCESS) return rc;
-        if (dtype_is_derived(dts[i]) && !(*out[i])->committed) {
-            set_error("datatype 0x%x is not committed", dts[i]);
-            return MPI_ERR_TYPE;
-        }
-    }
-    int rc = v_op_handle(op, r);
-    if (rc == MPI_SUCCESS)
-        rc = v_no_sum_wide(*r, "msx_accumulate_widen_dev (the target is the fp32 accumulator: use MPI_SUM)");
-    if (rc != MPI_SUCCESS) return rc;
-    switch (r->opidx) {
-    case O_SUM: case O_PROD: case O_MAX: case O_MIN: case O_REPLACE: case O_NOOP: break;
-    case O_NULL: set_error("msx_accumulate_widen_dev takes builtin ops only"); return MPI_ERR_OP;
-    default:
-        set_error("msx_accumulate_widen_dev takes MPI_SUM, MPI_PROD, MPI_MAX, MPI_MIN, MPI_REPLACE and MPI_NO_OP, not %s",
-                  op_name(r->opidx));
-        return MPI_ERR_OP;
-    }
-    return dt_accw2_plan(r->opidx, *ot, ocount, *tt, tcount, plan);
-}
-
-MSX_EXPORT int msx_accumulate_widen_plan(int64_t origin_count, MPI_Datatype origin_type, int64_t target_count,
-                                         MPI_Datatype target_type, MPI_Op op, int64_t* elements, int* path)
-{
-    if (!elements || !path) { set_error("null plan output"); return MPI_ERR_ARG; }
-    *elements = 0;
-    *path = 0;
-    OpRef r;
-    Dtype *ot, *tt;
-    AccW2Plan plan;
-    const int rc = accumulate_widen_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
-    if (rc != MPI_SUCCESS) return rc;
-    *elements = plan.elements;
-    *path = plan.path;
-    return MPI_SUCCESS;
-}
-
-MSX_EXPORT int msx_accumulate_widen_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
-                                        void* target, int64_t target_count, MPI_Datatype target_type, MPI_Op op,
-                                        void* stream)
-{
-    OpRef r;
-    Dtype *ot, *tt;
-    AccW2Plan plan;
-    int rc = accumulate_widen_plan(origin_count, origin_type, target_count, target_type, op, &r, &ot, &tt, &plan);
-    if (rc != MPI_SUCCESS || plan.path == 0) return rc;
-    if (!origin || !target) { set_error("null buffer"); return MPI_ERR_BUFFER; }
-    rc = ensure_device();
-    if (rc != MPI_SUCCESS) return rc;
-    return dt_accw2_dev(r.opidx, ot, origin, tt, target, plan, static_cast<hipStream_t>(stream));
-}
-
-// ---- msx_accumulate_batch_dev: many typed combines in few launches ---------------
-// Checks 2 - 7 of msx.h in their order (2 for the four arrays a plan takes)
-// and, when they pass, the plan.  One function behind the plan entry and the
-// real call; it never touches a GPU.
-static int accumulate_batch_plan(const int64_t* ocount, const MPI_Datatype* odt, const int64_t* tcount,
-                                 const MPI_Datatype* tdt, int nseg, MPI_Op op, OpRef* r, Acc2BatchPlan* plan)
-{
-    if (nseg < 0 || !ocount || !odt || !tcount || !tdt) { set_error("bad segment arrays (nseg=%d)", nseg); return MPI_ERR_ARG; }
-    for (int i = 0; i < nseg; ++i)
-        if (ocount[i] < 0 || tcount[i] < 0) { set_error("negative count in segment %d", i); return MPI_ERR_COUNT; }
-    std::vector<const Dtype*> ot((size_t)nseg), tt((size_t)nseg);
-    for (int i = 0; i < nseg; ++i) {
-        const MPI_Datatype dts[2] = {odt[i], tdt[i]};
-        const Dtype** out[2] = {&ot[(size_t)i], &tt[(size_t)i]};
-        for (int j = 0; j < 2; ++j) {
-            Dtype* t = nullptr;
-            const int rc = v_handle(dts[j], &t);
-            if (rc != MPI_SUCCESS) {
-                const std::string why = last_error();
-                set_error("segment %d: %s", i, why.c_str());
-                return rc;
-            }
-            if (dtype_is_derived(dts[j]) && !t->committed) {
-                set_error("segment %d: datatype 0x%x is not committed", i, dts[j]);
-                return MPI_ERR_TYPE;
-            }
-            *out[j] = t;
-        }
-    }
-    int rc = v_op_handle(op, r);
-    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(*r, "msx_accumulate_batch_dev (one combine per element: use MPI_SUM)");
-    if (rc != MPI_SUCCESS) return rc;
-    if (r->opidx == O_NULL) { set_error("msx_accumulate_batch_dev takes builtin ops only"); return MPI_ERR_OP; }
-    return dt_acc2_batch_plan(r->opidx, ot.data(), ocount, tt.data(), tcount, nseg, plan);
-}
-
-MSX_EXPORT int msx_accumulate_batch_plan(const int64_t* origin_count, const MPI_Datatype* origin_type,
-                                         const int64_t* target_count, const MPI_Datatype* target_type, int nseg,
-                                         MPI_Op op, int* width, int64_t* fuse_below, int* launches, int* batched,
-                                         int* single)
-{
-    if (!width || !fuse_below || !launches || !batched || !single) { set_error("null plan output"); return MPI_ERR_ARG; }
-    *width = acc2_batch_width();
-    *fuse_below = acc2_batch_fuse_below();
-    *launches = *batched = *single = 0;
-    if (nseg == 0) return MPI_SUCCESS;
-    OpRef r;
-    Acc2BatchPlan plan;
-    const int rc = accumulate_batch_plan(origin_count, origin_type, target_count, target_type, nseg, op, &r, &plan);
-    if (rc != MPI_SUCCESS) return rc;
-    *launches = plan.launches();
-    *batched = plan.fused;
-    *single = plan.single;
-    return MPI_SUCCESS;
-}
-
-MSX_EXPORT int msx_accumulate_batch_dev(const void* const* origin, const int64_t* origin_count,
-                                        const MPI_Datatype* origin_type, void* const* target,
-                                        const int64_t* target_count, const MPI_Datatype* target_type, int nseg,
-                                        MPI_Op op, void* stream)
-{
-    if (nseg == 0) return MPI_SUCCESS;
-    if (!origin || !target) { set_error("bad segment arrays (nseg=%d)", nseg); return MPI_ERR_ARG; }
-    OpRef r;
-    Acc2BatchPlan plan;
-    int rc = accumulate_batch_plan(origin_count, origin_type, target_count, target_type, nseg, op, &r, &plan);
-    if (rc != MPI_SUCCESS || plan.steps.empty()) return rc;
-    for (const Acc2BatchStep& st : plan.steps)
-        if (!origin[st.seg] || !target[st.seg]) { set_error("null buffer in segment %d", st.seg); return MPI_ERR_BUFFER; }
-    // two segments with one target address and one target datatype handle map
-    // the same first element: they certainly collide (spans are not compared:
-    // disjoint maps may interleave)
-    std::vector<const Acc2BatchStep*> by_target;
-    for (const Acc2BatchStep& st : plan.steps) by_target.push_back(&st);
-    auto key = [&](const Acc2BatchStep* st) { return std::make_pair((uintptr_t)target[st->seg], target_type[st->seg]); };
-    std::sort(by_target.begin(), by_target.end(), [&](const Acc2BatchStep* a, const Acc2BatchStep* b) {
-        return key(a) != key(b) ? key(a) < key(b) : a->seg < b->seg;
-    });
-    for (size_t j = 1; j < by_target.size(); ++j)
-        if (key(by_target[j]) == key(by_target[j - 1])) {
-            set_error("target of segment %d is the target of segment %d (same address, same datatype)",
-                      by_target[j]->seg, by_target[j - 1]->seg);
-            return MPI_ERR_BUFFER;
-        }
-    rc = ensure_device();
-    if (rc != MPI_SUCCESS) return rc;
-    return dt_acc2_batch_dev(r.opidx, plan, origin, target, static_cast<hipStream_t>(stream));
-}
-
-// ---- msx_get_accumulate_dev: fetch and combine between three datatype layouts ----
-// Checks 1 - 6 of msx.h in their order and, when they pass, the plan.  One
-// function behind the plan entry and the real call; it never touches a GPU.
-// *ot stays null under MPI_NO_OP: the origin triple is ignored there.
-static int get_accumulate_plan(int64_t ocount, MPI_Datatype odt, int64_t rcount, MPI_Datatype rdt, int64_t tcount,
-                               MPI_Datatype tdt, MPI_Op op, OpRef* r, Dtype** ot, Dtype** rt, Dtype** tt,
-                               Acc3Plan* plan)
-{
-    const bool noop = op == MPI_NO_OP;
-    if ((!noop && ocount < 0) || rcount < 0 || tcount < 0) { set_error("negative count"); return MPI_ERR_COUNT; }
-    const MPI_Datatype dts[3] = {odt, rdt, tdt};
-    Dtype** out[3] = {ot, rt, tt};
-    *ot = nullptr;
-    for (int i = noop ? 1 : 0; i < 3; ++i) {
-        int rc = v_handle(dts[i], out[i]);
-        if (rc != MPI_SUCCESS) return rc;
-        if (dtype_is_derived(dts[i]) && !(*out[i])->committed) {
-            set_error("datatype 0x%x is not committed", dts[i]);
-            return MPI_ERR_TYPE;
-        }
-    }
-    int rc = v_op_handle(op, r);
-    if (rc == MPI_SUCCESS) rc = v_no_sum_wide(*r, "msx_get_accumulate_dev (one combine per element: use MPI_SUM)");
-    if (rc != MPI_SUCCESS) return rc;
-    if (r->opidx == O_NULL) { set_error("msx_get_accumulate_dev takes builtin ops only"); return MPI_ERR_OP; }
-    return dt_gacc3_plan(r->opidx, *ot, ocount, *rt, rcount, *tt, tcount, plan);
-}
-
-MSX_EXPORT int msx_get_accumulate_plan(int64_t origin_count, MPI_Datatype origin_type, int64_t result_count,
-                                       MPI_Datatype result_type, int64_t target_count, MPI_Datatype target_type,
-                                       MPI_Op op, int64_t* elements, int* path, int* granule)
-{
-    if (!elements || !path || !granule) { set_error("null plan output"); return MPI_ERR_ARG; }
-    *elements = 0;
-    *path = *granule = 0;
-    OpRef r;
-    Dtype *ot, *rt, *tt;
-    Acc3Plan plan;
-    const int rc = get_accumulate_plan(origin_count, origin_type, result_count, result_type, target_count,
-                                       target_type, op, &r, &ot, &rt, &tt, &plan);
-    if (rc != MPI_SUCCESS) return rc;
-    *elements = plan.elements;
-    *path = plan.path;
-    *granule = plan.path ? plan.granule : 0;
-    return MPI_SUCCESS;
-}
-
-MSX_EXPORT int msx_get_accumulate_dev(const void* origin, int64_t origin_count, MPI_Datatype origin_type,
-                                      void* result, int64_t result_count, MPI_Datatype result_type, void* target,
-                                      int64_t target_count, MPI_Datatype target_type, MPI_Op op, void* stream)
-{
-    OpRef r;
-    Dtype *ot, *rt, *tt;
-    Acc3Plan plan;
-    int rc = get_accumulate_plan(origin_count, origin_type, result_count, result_type, target_count, target_type, op,
-                                 &r, &ot, &rt, &tt, &plan);
-    if (rc != MPI_SUCCESS || plan.path == 0) return rc;
-    if (!result || !target || (!origin && r.opidx != O_NOOP)) { set_error("null buffer"); return MPI_ERR_BUFFER; }
-    rc = ensure_device();
-    if (rc != MPI_SUCCESS) return rc;
-    return dt_gacc3_dev(r.opidx, ot, origin, rt, result_count, result, tt, target, plan,
-                        static_cast<hipStream_t>(stream));
 }
 
 // ---- PMPI_ profiling aliases --------------------------------------------------

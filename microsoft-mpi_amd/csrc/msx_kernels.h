@@ -58,12 +58,31 @@ struct CombineSeg {
 };
 hipError_t launch_combine_segs(int opidx, Kind k, const CombineSeg* segs, int nseg, hipStream_t s);
 
-// The two-layout datatype kernels (msx_acc2.hip, msx_acc2_segs.hip) divide in
-// 32 bits while the call's granule count and both instance sizes, in granules,
-// are below 2^32 (the magic divisions of msx_dtype_map.h).
-constexpr bool dt_map_narrow(int64_t n, int64_t gsize_o, int64_t gsize_t)
+struct DevLayout;   // msx_dtype.h
+// msx_pack.hip: packed <-> typed over `count` instances of one layout, and the
+// per-element combine of packed elements into the typed side
+hipError_t launch_dt_copy(const DevLayout& L, int64_t count, void* typed, void* packed, bool unpack,
+                          hipStream_t s);
+hipError_t launch_dt_acc(int opidx, Kind k, const DevLayout& L, int64_t count, const void* packed,
+                         void* typed, hipStream_t s);
+// msx_acc2.hip: n elements (a copy: `bytes` in granules of G) between two layouts
+hipError_t launch_dt_acc2(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lt,
+                          void* target, int64_t n, int align, hipStream_t s);
+hipError_t launch_dt_copy2(const DevLayout& Lo, const void* origin, const DevLayout& Lt, void* target,
+                           int64_t bytes, int G, hipStream_t s);
+// msx_acc3.hip: the fetch forms over three layouts
+hipError_t launch_dt_gacc3(int opidx, Kind k, const DevLayout& Lo, const void* origin, const DevLayout& Lr,
+                           void* result, const DevLayout& Lt, void* target, int64_t n, int align, hipStream_t s);
+hipError_t launch_dt_xchg3(const DevLayout& Lo, const void* origin, const DevLayout& Lr, void* result,
+                           const DevLayout& Lt, void* target, int64_t bytes, int G, hipStream_t s);
+
+// The two- and three-layout datatype kernels (msx_acc2.hip, msx_acc2_segs.hip,
+// msx_acc3.hip) divide in 32 bits while the call's granule count and every
+// side's instance size, in granules, are below 2^32 (the magic divisions of
+// msx_dtype_map.h).
+constexpr bool dt_map_narrow(int64_t n, int64_t gsize_o, int64_t gsize_t, int64_t gsize_r = 0)
 {
-    return n < 0xffffffffll && gsize_o < 0xffffffffll && gsize_t < 0xffffffffll;
+    return n < 0xffffffffll && gsize_o < 0xffffffffll && gsize_t < 0xffffffffll && gsize_r < 0xffffffffll;
 }
 
 // Many independent two-layout combines of one (op, kind) in ONE launch
@@ -77,7 +96,6 @@ constexpr bool dt_map_narrow(int64_t n, int64_t gsize_o, int64_t gsize_t)
 // pointers); the launch runs its aligned form when every segment allows it.
 // launch_dt_copy2_segs is MPI_REPLACE: bytes move in granules of the smallest
 // `align` of the launch.
-struct DevLayout;
 constexpr int kAcc2SegsWidth = 12;
 constexpr int64_t kAcc2SegsFuseBelow = (int64_t)4 << 20;     // measured: DESIGN.md §3b
 struct Acc2Seg {

@@ -8,7 +8,8 @@
 //
 // The launchers visit the map at compile time: for_op turns an op index into
 // an OpTag, for_kind a Kind into a TypeTag, and the visitor (a generic lambda)
-// instantiates its kernel launch on them.  A pair outside the map never
+// instantiates its kernel launch on them (for_granule does the same for the
+// byte movers' granule).  A pair outside the map never
 // instantiates anything and gives hipErrorInvalidValue.  The rule restates the
 // builtin ops' tables (op.cpp:739-1883) per kind; the handle-level legality
 // (op_legal_groups, msx_types.cpp) is checked before any launcher is reached
@@ -23,6 +24,7 @@ namespace msx {
 
 template <int OP> struct OpTag { static constexpr int value = OP; };
 template <class T> struct TypeTag { using type = T; };
+template <int G> struct GranTag { static constexpr int value = G; };
 
 // Classes of element kinds, as the ops' tables group them.
 enum KindClass : unsigned {
@@ -79,6 +81,20 @@ hipError_t for_op(int opidx, F&& f)
     case O_MINLOC: return f(OpTag<O_MINLOC>{});
     case O_MAXLOC: return f(OpTag<O_MAXLOC>{});
     default:       return hipErrorInvalidValue;
+    }
+}
+
+// f(GranTag<G>{}) for the granule of a byte mover: a power of two <= 16 (the
+// launchers check that before they ask).
+template <class F>
+hipError_t for_granule(int G, F&& f)
+{
+    switch (G) {
+    case 16: return f(GranTag<16>{});
+    case 8:  return f(GranTag<8>{});
+    case 4:  return f(GranTag<4>{});
+    case 2:  return f(GranTag<2>{});
+    default: return f(GranTag<1>{});
     }
 }
 

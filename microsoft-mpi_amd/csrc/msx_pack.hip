@@ -274,13 +274,7 @@ hipError_t run_copy(const CopyArgs& a, bool reg, hipStream_t s)
 template <bool UNPACK>
 hipError_t copy_g(int G, const CopyArgs& a, bool reg, hipStream_t s)
 {
-    switch (G) {
-    case 16: return run_copy<16, UNPACK>(a, reg, s);
-    case 8: return run_copy<8, UNPACK>(a, reg, s);
-    case 4: return run_copy<4, UNPACK>(a, reg, s);
-    case 2: return run_copy<2, UNPACK>(a, reg, s);
-    default: return run_copy<1, UNPACK>(a, reg, s);
-    }
+    return for_granule(G, [&](auto g) { return run_copy<decltype(g)::value, UNPACK>(a, reg, s); });
 }
 
 // One (op, element type) pair of msx_op_kind.h's map.

@@ -192,6 +192,7 @@ def lib():
                                             ctypes.POINTER(i), ctypes.POINTER(i)]),
         "msx_pack_dev": (i, [p, i64, i, p, p]),
         "msx_unpack_dev": (i, [p, i64, i, p, p]),
+        # the typed accumulate family (msx_api_acc.cpp)
         "msx_accumulate_dev": (i, [p, i64, i, p, i64, i, i, p]),
         "msx_accumulate_plan": (i, [i64, i, i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i), ctypes.POINTER(i)]),
         "msx_accumulate_widen_dev": (i, [p, i64, i, p, i64, i, i, p]),

@@ -95,10 +95,11 @@ def _same(got, exp, tag):
                 f"got {int(got[i]):#04x} exp {int(exp[i]):#04x}")
 
 
-def _run(L, op, dt, orec, ocount, trec, tcount, path, mis_o=0, mis_t=0, seed=0):
+def _run(L, op, dt, orec, ocount, trec, tcount, path, mis_o=0, mis_t=0, seed=0, data=None):
     """One msx_accumulate_dev call checked as the module docstring says.
     dt: the element datatype's name for an op, None for MPI_REPLACE / MPI_NO_OP
-    (random bytes).  Returns the plan."""
+    (random bytes).  data: the (origin, target) data bytes in type-map order for
+    a directed case, instead of _data's.  Returns the plan."""
     keep = []
     oh, th = _commit(L, orec, keep), _commit(L, trec, keep)
     ot, tt = build_oracle(orec), build_oracle(trec)
@@ -108,7 +109,10 @@ def _run(L, op, dt, orec, ocount, trec, tcount, path, mis_o=0, mis_t=0, seed=0):
     ob, tb = _data_bytes(ot, ocount, bo), _data_bytes(tt, tcount, bt)
     nb = ob.size
     assert nb <= tb.size and len(set(tb.tolist())) == tb.size          # a legal target map
-    if dt is None:
+    if data is not None:
+        assert data[0].size == nb and data[1].size == tb.size
+        img_o[ob], img_t[tb] = data
+    elif dt is None:
         img_o[ob] = rng.integers(0, 256, nb, dtype=np.uint8)
         img_t[tb] = rng.integers(0, 256, tb.size, dtype=np.uint8)
     else:
